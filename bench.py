@@ -11,7 +11,14 @@ per GPU that are already resident in HBM.  Metric: images/s of PPYOLO ResNet50-v
 bs=8 (BASELINE.json `metric`, configs[2]); weak scaling (8 images per GPU, one RCCL
 all-gather of the detection records per step when N > 1).  Prints ONE JSON line on rank 0.
 
-`roofline`: the dominant kernels are the fp32-MFMA implicit-GEMM convolutions.  After the
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step` = wall time of the timed
+region / K).  `--dump-outputs DIR` also writes what the last timed step computed (the padded detections, counts and keep
+indices of `PPYOLO.forward_padded`) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for
+output.  Everything else the benchmark measures -- `sustained`, `one_batch_at_a_time`, `roofline`, `roofline_other`, the other
+math modes, host input and pre-processing, `cpu_baseline`, `parity_note`, `worst_case_regime` (and for --train the plain loop,
+`cpu_baseline`, `value_fp32_exact` and the PMC traffic) -- runs only with `--full`.
+
+`roofline` (--full): the dominant kernels are the fp32-MFMA implicit-GEMM convolutions.  After the
 timed region the same plan is replayed eagerly with HIP events bracketing every conv / DCN
 launch on the launch stream; achieved = algorithmic conv FLOPs per step (2*MAC, BN/act
 excluded: 102.0 GFLOP per image at R50-608) / summed conv launch time, against
@@ -76,6 +83,26 @@ def model_from_sd(cfg_name, sd, device):
     m.eval()
     hd.set_dropblock(is_test=True)
     return m.to(device)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one path/<name>.npy per tensor of `arrays` (name -> tensor), float32 for floating tensors up to 32 bits,
+    float64 otherwise (integer counts and indices stay exact).  A tensor larger than its equal share of DUMP_BUDGET_BYTES is
+    written as path/<name>_sample.npy: its flattened elements at sorted indices drawn with a fixed seed (the same for every run
+    with the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        v = t.detach().cpu().numpy()
+        v = v.astype(np.float32 if v.dtype.kind == 'f' and v.itemsize <= 4 else np.float64)
+        if v.nbytes > share:
+            idx = np.unique(np.random.RandomState(0).randint(0, v.size, share // v.itemsize))
+            v, name = v.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(path, name + '.npy'), v)
 
 
 def worst_case_leg(wl, dev, x, ims, sd, cfg, depth, seconds, cpu_threads):
@@ -1037,11 +1064,13 @@ def train_bench(a, wl, dev, rank, world):
     loop(a.steps, pre)
     barrier()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                    # the last timed step's loss terms and (averaged) gradients
+        dump_outputs(a.dump_outputs, dict(loss=losses[-1], grad=ts.gflat))
     if a.dump_dets and rank == 0:                       # tests: the averaged gradients of the last timed step
         torch.cuda.synchronize()
         np.save(a.dump_dets, ts.gflat.cpu().numpy())
     dt_plain = None
-    if pre and world == 1 and not a.dump_dets:
+    if a.full and pre and world == 1 and not a.dump_dets:
         ts._pref = None
         loop(2, False)
         barrier()
@@ -1082,11 +1111,11 @@ def train_bench(a, wl, dev, rank, world):
         if dt_plain is not None:
             out['one_step_at_a_time'] = dict(value=round(world * a.batch * a.steps / dt_plain, 2), unit='images/s', ms_per_step=round(dt_plain / a.steps * 1e3, 3),
                                              note='the plain loop: step(x) without the next batch (what the reference\'s loop does, train.py:416-443)')
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = train_cpu_baseline(sd, cfg, x, gt, targets)
         # `value_fp32_exact` (round 5): the same step with every convolution, data gradient and weight gradient on the exact-fp32 MFMA
         # -- its own process, because the kernel choices are read once per process
-        if world == 1 and not a.no_alt_math and os.environ.get('PPYOLO_HIP_TRAIN_MATH', 'f16x2') != 'fp32':
+        if a.full and world == 1 and not a.no_alt_math and os.environ.get('PPYOLO_HIP_TRAIN_MATH', 'f16x2') != 'fp32':
             import subprocess
             env = dict(os.environ, PPYOLO_HIP_TRAIN_MATH='fp32', PPY_WGRAD_FP32='1', PPY_DGRAD_FP32='1')
             cmd = [sys.executable, os.path.abspath(__file__), '--train', '--steps', str(min(a.steps, 10)), '--warmup', '2', '--no-cpu-baseline',
@@ -1104,7 +1133,7 @@ def train_bench(a, wl, dev, rank, world):
         # HBM-side bytes of the convolution launches (forward, data gradient, weight gradient), MEASURED BY THIS RUN like the inference
         # line's: two rocprofv3 --pmc child passes of three eager steps; the committed summary only as a fallback, marked stale
         measured = None
-        if world == 1 and not a.no_pmc and a.workload == 'r50vd_608':
+        if a.full and world == 1 and not a.no_pmc and a.workload == 'r50vd_608':
             measured, src = pmc_traffic_leg(['--train', '--workload', a.workload, '--batch', str(a.batch)], None, timeout=300,
                                             extra_kernels=('conv_wgrad',))
             if measured is not None:
@@ -1114,7 +1143,7 @@ def train_bench(a, wl, dev, rank, world):
                 out['roofline']['traffic_source'] = src
         import glob
         files = sorted(glob.glob(os.path.join(ROOT, 'profiles', 'r*_train_pmc_traffic.json')))
-        if measured is None and files and a.workload == 'r50vd_608' and a.batch == 8 and ts.freeze_at == 5:
+        if a.full and measured is None and files and a.workload == 'r50vd_608' and a.batch == 8 and ts.freeze_at == 5:
             with open(files[-1]) as fh:
                 rec = json.load(fh)
             out['roofline']['traffic'] = round(rec['hbm_bytes_per_step'] / max(1, rec['conv_launches_per_step']))
@@ -1152,7 +1181,7 @@ def main():
                     'the best NEIGHBOUR of a second lane (HipExecutor.co_tune)')
     ap.add_argument('--verbose-tune', action='store_true')
     ap.add_argument('--save-tuning', default=None, help='write the measured table to this JSON file')
-    ap.add_argument('--layer-report', default=None, help='write per-launch timings to this JSON file')
+    ap.add_argument('--layer-report', default=None, help='write per-launch timings to this JSON file (implies --full)')
     ap.add_argument('--backend', default=None, help='torch.distributed backend (default nccl = RCCL); "gloo" '
                     'together with --share-gpu lets the N>1 code path be smoke-tested on a 1-GPU box')
     ap.add_argument('--share-gpu', action='store_true', help='all ranks use cuda:0 (smoke test only)')
@@ -1167,18 +1196,24 @@ def main():
     ap.add_argument('--pmc-child', action='store_true', help='(internal) the short eager one-lane run the PMC passes profile')
     ap.add_argument('--trace-child', action='store_true', help='(internal) the eager one-lane run with op markers that kernel_trace_leg profiles')
     ap.add_argument('--no-kernel-trace', action='store_true', help='skip the rocprofv3 --kernel-trace child pass (roofline.trace)')
-    ap.add_argument('--trace-layers', default=None, help='write the trace-derived per-op table (text) to this file')
+    ap.add_argument('--trace-layers', default=None, help='write the trace-derived per-op table (text) to this file (implies --full)')
     ap.add_argument('--tune-cu-mask', default=None, help='with --autotune: measure the layers on a stream restricted to these CUs (one term of '
                     'runtime.lane_cu_masks, e.g. m256:0-127 = half of every XCD) -- the table a CU-masked lane would want')
     ap.add_argument('--no-prefetch', action='store_true', help='--train: the plain loop (no backbone prefetch of the next batch)')
     ap.add_argument('--lane-phase', type=float, default=0.0, help='diagnostic: start lane 1 this fraction of a one-lane step behind lane 0 (a spin '
                     'kernel on its stream, once, before the steady-state loop): do the lanes run in lockstep, and would an offset help?')
-    ap.add_argument('--power-trace', action='store_true', help='sample rocm-smi (socket power, shader clock) during the `sustained` loop')
+    ap.add_argument('--power-trace', action='store_true', help='sample rocm-smi (socket power, shader clock) during the `sustained` loop (implies --full)')
     ap.add_argument('--no-batch-scaling', action='store_true', help='skip roofline.batch_scaling (one lane at batch 8 / 16 / 32 on the batch-8 kernels)')
     ap.add_argument('--no-worst-case', action='store_true', help='skip the whole-step measurement in the all-pass score regime')
     ap.add_argument('--min-seconds', type=float, default=2.0, help='steady-state running before the timed K steps and '
                     'length of the `sustained` measurement (the board is power-managed: DESIGN.md 4.1)')
+    ap.add_argument('--full', action='store_true', help='also run every side measurement (sustained, one lane, roofline, other '
+                    'math modes, host input, pre-processing, CPU baseline, parity note, worst case); a plain run times the K steps only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy '
+                    '(float32 / float64, at most 64 MB in all)')
     a = ap.parse_args()
+    if a.layer_report or a.trace_layers or a.power_trace:
+        a.full = True          # what they write comes from the --full legs
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # bare `python bench.py --gpus N`: start the N ranks ourselves (one process per GPU)
@@ -1325,10 +1360,17 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if a.dump_outputs and rank == 0:
+        k_last = (it[0] - 1) % depth
+        e_last = lanes[k_last][0]
+        arrays = dict(dets=e_last.out_dets, count=e_last.out_count, keep=e_last.out_keep)
+        if world > 1:
+            arrays['gathered'] = gats[k_last].all          # [world * batch, keep_top_k + 1, 6]: row keep_top_k holds the count
+        dump_outputs(a.dump_outputs, arrays)
 
     # `sustained`: the same loop over at least --min-seconds (a multiple of K steps), timed the same way
     sustained, power = None, None
-    if a.min_seconds > 0:
+    if a.full and a.min_seconds > 0:
         n_sus = a.steps * max(1, int(a.min_seconds / max(dt, 1e-6)) + 1)
         barrier()
         smi = _SmiSampler() if (a.power_trace and rank == 0) else None
@@ -1377,7 +1419,7 @@ def main():
                      per_rank_images_per_s=[round(float(v), 1) for v in allr[:, 0]],
                      devices=['cuda:%d' % int(v) for v in allr[:, 1]])
     one_at_a_time = None
-    if depth > 1 and world == 1:              # not `value`: the same steps with one batch on the device at a time
+    if a.full and depth > 1 and world == 1:              # not `value`: the same steps with one batch on the device at a time
         torch.cuda.synchronize()
         n1, dt1 = min(a.steps, 30), 0.0
         with torch.cuda.stream(lanes[0][1]):
@@ -1393,70 +1435,6 @@ def main():
         one_at_a_time = round(a.batch * n1 / dt1, 1)
 
     if rank == 0:
-        total_flops, per_op = conv_flops(ex.plan)
-        conv_ms, covered, nconv, ideal_s, fam_flops = timed_conv_pass(ex, per_op)
-        peak = covered / ideal_s / 1e12        # flop-weighted peak of the kernel mix of this step
-        # Round 6 (review item 3): the solo kernel time comes from PROFILER TIMESTAMPS of a one-lane eager child of this run where
-        # rocprofv3 is available (kernel_trace_leg); an event pair around a launch also times two event packets (~2.5 us per
-        # launch, 5 % over 75 launches: `hip_events_over_trace`), so the HIP-event sum is kept beside it as the cross-check.
-        conv_ms_events, timing = conv_ms, 'HIP events around every conv / DCN launch of an eager pass (best of 3)'
-        ktrace = None
-        if world == 1 and not a.no_kernel_trace:
-            ktrace, ktab = kernel_trace_leg(['--workload', a.workload, '--batch', str(a.batch)], ex, per_op, table_path=a.trace_layers)
-            if ktrace is None:
-                ktrace = dict(error=ktab)
-            else:
-                ktrace['hip_events_over_trace'] = round(conv_ms_events / ktrace['kernel_ms_per_step'], 4)
-                conv_ms = ktrace['kernel_ms_per_step']
-                timing = ('rocprofv3 --kernel-trace timestamps of an eager one-lane child of this run (sum of End - Start of the conv / DCN '
-                          'launches\' kernels, mean of %d passes)' % ktrace['passes'])
-        achieved = covered / (conv_ms * 1e-3) / 1e12
-        # HBM-side bytes of the conv launches from rocprofv3 PMC passes (collected separately with
-        # tools/prof_run.sh; summary committed under profiles/): average per launch, like `achieved`
-        traffic, traffic_src = None, None
-        why_stale = '--no-pmc' if a.no_pmc else 'N > 1'
-        if world == 1 and not a.no_pmc:
-            traffic, traffic_src = pmc_traffic_leg(['--workload', a.workload, '--batch', str(a.batch)], nconv)
-            if traffic is None:
-                why_stale, traffic_src = traffic_src, None
-        if traffic is None and a.workload == 'r50vd_608' and a.batch == 8:
-            import glob
-            files = sorted(f for f in glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_traffic.json')) if '_train_' not in os.path.basename(f))
-            if files:
-                with open(files[-1]) as fh:
-                    rec = json.load(fh)
-                traffic = round(rec['hbm_bytes_per_step'] / nconv)
-                traffic_src = dict(file='profiles/' + os.path.basename(files[-1]), measured=rec.get('measured', 'round 1'), stale=True,
-                                   note='NOT measured by this run (%s): committed rocprofv3 PMC summary of the named date '
-                                        '(tools/prof_run.sh -> tools/pmc_traffic.py)' % why_stale)
-        mfma_pmc = traffic_src.pop('mfma_busy_pmc', None) if traffic_src else None
-        roof = dict(bound='mfma', achieved=round(achieved, 2), peak=round(peak, 1), unit='TFLOP/s',
-                    frac=round(achieved / peak, 4), mfma_busy_pmc=mfma_pmc, traffic=traffic, traffic_source=traffic_src,
-                    traffic_unit='bytes per launch (mean over the conv launches of a step; PMC 2*FETCH_SIZE+WRITE_SIZE)',
-                    kernel='conv_igemm_x3_kernel<*> (fp32-in/fp32-out implicit GEMM on the 16-bit MFMA: f16x2 = 3 x '
-                           'v_mfma_f32_32x32x16_f16 per product after a 2-term fp16 split, bf16x3 = 6 x ..._bf16 after a 3-term '
-                           'bf16 split) / conv_igemm_glds_kernel<*> (v_mfma_f32_32x32x2_f32), %d launches/step' % nconv,
-                    peak_note='achieved = algorithmic fp32 FLOPs / solo kernel time of the conv launches (kernel_ms_per_step; timing: ' + timing + '); peak = the same '
-                              'FLOPs / MFMA-pipe time at peak, pricing a launch by its kernel family: f16x2 %.1f (= dense '
-                              '16-bit MFMA %.1f / 3 products per multiply-add), bf16x3 %.1f (/ 6), exact fp32 %.1f TFLOP/s; '
-                              'FLOP shares: %s.  Peaks are at the nominal 2.4 GHz; under dense 16-bit MFMA on real '
-                              'operands the board runs at its 1400 W power cap and ~1.8-2.1 GHz (DESIGN.md 4.1)' % (
-                                  F16X2_PEAK_TFLOPS, BF16_MFMA_PEAK_TFLOPS, X3_PEAK_TFLOPS, FP32_MFMA_PEAK_TFLOPS,
-                                  ', '.join('%s %.1f%%' % (k, 100.0 * v / max(1, covered)) for k, v in fam_flops.items())),
-                    achieved_vs_fp32_mfma_peak=round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
-                    flops_per_step=covered, kernel_ms_per_step=round(conv_ms, 4), kernel_ms_per_step_hip_events=round(conv_ms_events, 3),
-                    kernel_timing=timing, trace=ktrace,
-                    whole_step_mfma_util=round(total_flops / (ms_per_step * 1e-3) / 1e12 / peak, 4))
-        if one_at_a_time is not None:
-            ms_one = a.batch / one_at_a_time * 1e3
-            roof['frac_one_lane'] = round(total_flops / (ms_one * 1e-3) / 1e12 / peak, 4)
-            roof['overlap'] = dict(ms_per_step_one_lane=round(ms_one, 3), ms_per_step_two_lanes=round(ms_per_step, 3),
-                                   hidden_fraction=round(1.0 - ms_per_step / ms_one, 4), conv_kernel_ms_per_step_solo=round(conv_ms, 3),
-                                   note='frac = conv FLOPs / SOLO conv kernel time (eager launches, HIP events); frac_one_lane / '
-                                        'whole_step_mfma_util = the same FLOPs / whole-step wall time with one / %d batches in flight; '
-                                        'hidden_fraction = share of a one-lane step the second lane hides.  Per-stream busy time and '
-                                        'the overlap of the two lanes from a rocprofv3 kernel trace of this loop: '
-                                        'profiles/r04_two_lane_timeline.txt (tools/two_lane_timeline.py)' % depth)
         out = dict(metric='images/sec PPYOLO R50-vd 608x608 bs=8' if a.workload == 'r50vd_608'
                    else 'images/sec %s bs=%d' % (a.workload, a.batch),
                    value=round(value, 2), unit='images/s', n_gpus=world, steps=a.steps, warmup=a.warmup,
@@ -1479,50 +1457,116 @@ def main():
                                                           'terms, 6 partial products; error vs fp64 <= the fp32 fma chain)'
                                                 }.get(ex.math, ''),
                                tile_table='re-measured' if a.autotune else os.path.basename(_tuned_path(ex.math))),
-                   roofline=roof, ranks=ranks)
-        if sustained is not None:
-            out['sustained'] = sustained
-            if power is not None:
-                out['sustained']['power'] = power
-        if one_at_a_time is not None:
-            out['one_batch_at_a_time'] = dict(value=one_at_a_time, unit='images/s',
-                                              note='the graph of lane 0 replayed alone (= --in-flight 1)')
-        if world == 1 and not a.no_batch_scaling and a.batch == 8:
-            roof['batch_scaling'] = batch_scaling_leg(model, wl, dev, ex)
-        out['roofline_other'] = decode_nms_leg(ex)
-        hbm_conv = hbm_conv_leg(ex)
-        if hbm_conv is not None:
-            out['roofline_other']['expand_1x1'] = hbm_conv
-        fused = b2b_leg(ex)
-        if fused is not None:
-            out['roofline_other']['conv3x3_conv1x1'] = fused
-        if a.layer_report:
-            layer_report(ex, per_op, a.layer_report)
-        if world == 1 and not a.no_alt_math:
-            out['alt_math'] = alt_math_leg(wl, dev, x, ims, min(a.steps, 30), ex.math, depth)
-            if ex.math != 'fp32' and 'fp32' in out['alt_math']:
-                # `value` computes every product from 2-term fp16 splits (3 MFMA products, ~22-bit operands, fp32 accumulate);
-                # this is the same step with every convolution on the exact-fp32 MFMA, v_mfma_f32_32x32x2_f32
-                out['value_fp32_exact'] = out['alt_math']['fp32']
-                out['value_fp32_exact_note'] = ('same loop, every convolution on the exact-fp32 MFMA (PPYOLO_HIP_MATH=fp32): %.2f of the '
-                                                '157.3 TFLOP/s fp32-MFMA bound' % (out['alt_math']['fp32'] * total_flops / a.batch / 1e12 / FP32_MFMA_PEAK_TFLOPS))
-        if world == 1 and not a.no_host_input:
-            out['host_input'] = host_input_leg(ex, x, ims, min(a.steps, 30), lanes)
-        if world == 1 and not a.no_host_input:
-            out['roofline_other']['preprocess'] = preprocess_leg(cfg, wl['size'], a.batch, lanes, min(a.steps, 30),
-                                                                 not a.no_cpu_baseline)
-        if world == 1 and not a.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline(sd, cfg, wl['size'], a.batch)
-        if world == 1:
-            try:
-                pn = parity_note_leg(model, wl, a.batch, x)
-            except Exception as exc:          # (a diagnostic field must not take the benchmark line with it)
-                pn = dict(error='%s: %s' % (type(exc).__name__, exc))
-            if pn is not None:
-                out['parity_note'] = pn
-        if world == 1 and not a.no_worst_case:
-            out['worst_case_regime'] = worst_case_leg(wl, dev, x, ims, sd, cfg, depth, min(a.min_seconds, 1.0) or 0.2,
-                                                      out['cpu_baseline']['cores'] if 'cpu_baseline' in out else 0)
+                   ranks=ranks)
+        if a.full:
+            total_flops, per_op = conv_flops(ex.plan)
+            conv_ms, covered, nconv, ideal_s, fam_flops = timed_conv_pass(ex, per_op)
+            peak = covered / ideal_s / 1e12        # flop-weighted peak of the kernel mix of this step
+            # Round 6 (review item 3): the solo kernel time comes from PROFILER TIMESTAMPS of a one-lane eager child of this run where
+            # rocprofv3 is available (kernel_trace_leg); an event pair around a launch also times two event packets (~2.5 us per
+            # launch, 5 % over 75 launches: `hip_events_over_trace`), so the HIP-event sum is kept beside it as the cross-check.
+            conv_ms_events, timing = conv_ms, 'HIP events around every conv / DCN launch of an eager pass (best of 3)'
+            ktrace = None
+            if world == 1 and not a.no_kernel_trace:
+                ktrace, ktab = kernel_trace_leg(['--workload', a.workload, '--batch', str(a.batch)], ex, per_op, table_path=a.trace_layers)
+                if ktrace is None:
+                    ktrace = dict(error=ktab)
+                else:
+                    ktrace['hip_events_over_trace'] = round(conv_ms_events / ktrace['kernel_ms_per_step'], 4)
+                    conv_ms = ktrace['kernel_ms_per_step']
+                    timing = ('rocprofv3 --kernel-trace timestamps of an eager one-lane child of this run (sum of End - Start of the conv / DCN '
+                              'launches\' kernels, mean of %d passes)' % ktrace['passes'])
+            achieved = covered / (conv_ms * 1e-3) / 1e12
+            # HBM-side bytes of the conv launches from rocprofv3 PMC passes (collected separately with
+            # tools/prof_run.sh; summary committed under profiles/): average per launch, like `achieved`
+            traffic, traffic_src = None, None
+            why_stale = '--no-pmc' if a.no_pmc else 'N > 1'
+            if world == 1 and not a.no_pmc:
+                traffic, traffic_src = pmc_traffic_leg(['--workload', a.workload, '--batch', str(a.batch)], nconv)
+                if traffic is None:
+                    why_stale, traffic_src = traffic_src, None
+            if traffic is None and a.workload == 'r50vd_608' and a.batch == 8:
+                import glob
+                files = sorted(f for f in glob.glob(os.path.join(ROOT, 'profiles', 'r*_pmc_traffic.json')) if '_train_' not in os.path.basename(f))
+                if files:
+                    with open(files[-1]) as fh:
+                        rec = json.load(fh)
+                    traffic = round(rec['hbm_bytes_per_step'] / nconv)
+                    traffic_src = dict(file='profiles/' + os.path.basename(files[-1]), measured=rec.get('measured', 'round 1'), stale=True,
+                                       note='NOT measured by this run (%s): committed rocprofv3 PMC summary of the named date '
+                                            '(tools/prof_run.sh -> tools/pmc_traffic.py)' % why_stale)
+            mfma_pmc = traffic_src.pop('mfma_busy_pmc', None) if traffic_src else None
+            roof = dict(bound='mfma', achieved=round(achieved, 2), peak=round(peak, 1), unit='TFLOP/s',
+                        frac=round(achieved / peak, 4), mfma_busy_pmc=mfma_pmc, traffic=traffic, traffic_source=traffic_src,
+                        traffic_unit='bytes per launch (mean over the conv launches of a step; PMC 2*FETCH_SIZE+WRITE_SIZE)',
+                        kernel='conv_igemm_x3_kernel<*> (fp32-in/fp32-out implicit GEMM on the 16-bit MFMA: f16x2 = 3 x '
+                               'v_mfma_f32_32x32x16_f16 per product after a 2-term fp16 split, bf16x3 = 6 x ..._bf16 after a 3-term '
+                               'bf16 split) / conv_igemm_glds_kernel<*> (v_mfma_f32_32x32x2_f32), %d launches/step' % nconv,
+                        peak_note='achieved = algorithmic fp32 FLOPs / solo kernel time of the conv launches (kernel_ms_per_step; timing: ' + timing + '); peak = the same '
+                                  'FLOPs / MFMA-pipe time at peak, pricing a launch by its kernel family: f16x2 %.1f (= dense '
+                                  '16-bit MFMA %.1f / 3 products per multiply-add), bf16x3 %.1f (/ 6), exact fp32 %.1f TFLOP/s; '
+                                  'FLOP shares: %s.  Peaks are at the nominal 2.4 GHz; under dense 16-bit MFMA on real '
+                                  'operands the board runs at its 1400 W power cap and ~1.8-2.1 GHz (DESIGN.md 4.1)' % (
+                                      F16X2_PEAK_TFLOPS, BF16_MFMA_PEAK_TFLOPS, X3_PEAK_TFLOPS, FP32_MFMA_PEAK_TFLOPS,
+                                      ', '.join('%s %.1f%%' % (k, 100.0 * v / max(1, covered)) for k, v in fam_flops.items())),
+                        achieved_vs_fp32_mfma_peak=round(achieved / FP32_MFMA_PEAK_TFLOPS, 4),
+                        flops_per_step=covered, kernel_ms_per_step=round(conv_ms, 4), kernel_ms_per_step_hip_events=round(conv_ms_events, 3),
+                        kernel_timing=timing, trace=ktrace,
+                        whole_step_mfma_util=round(total_flops / (ms_per_step * 1e-3) / 1e12 / peak, 4))
+            if one_at_a_time is not None:
+                ms_one = a.batch / one_at_a_time * 1e3
+                roof['frac_one_lane'] = round(total_flops / (ms_one * 1e-3) / 1e12 / peak, 4)
+                roof['overlap'] = dict(ms_per_step_one_lane=round(ms_one, 3), ms_per_step_two_lanes=round(ms_per_step, 3),
+                                       hidden_fraction=round(1.0 - ms_per_step / ms_one, 4), conv_kernel_ms_per_step_solo=round(conv_ms, 3),
+                                       note='frac = conv FLOPs / SOLO conv kernel time (eager launches, HIP events); frac_one_lane / '
+                                            'whole_step_mfma_util = the same FLOPs / whole-step wall time with one / %d batches in flight; '
+                                            'hidden_fraction = share of a one-lane step the second lane hides.  Per-stream busy time and '
+                                            'the overlap of the two lanes from a rocprofv3 kernel trace of this loop: '
+                                            'profiles/r04_two_lane_timeline.txt (tools/two_lane_timeline.py)' % depth)
+            out['roofline'] = roof
+            if sustained is not None:
+                out['sustained'] = sustained
+                if power is not None:
+                    out['sustained']['power'] = power
+            if one_at_a_time is not None:
+                out['one_batch_at_a_time'] = dict(value=one_at_a_time, unit='images/s',
+                                                  note='the graph of lane 0 replayed alone (= --in-flight 1)')
+            if world == 1 and not a.no_batch_scaling and a.batch == 8:
+                roof['batch_scaling'] = batch_scaling_leg(model, wl, dev, ex)
+            out['roofline_other'] = decode_nms_leg(ex)
+            hbm_conv = hbm_conv_leg(ex)
+            if hbm_conv is not None:
+                out['roofline_other']['expand_1x1'] = hbm_conv
+            fused = b2b_leg(ex)
+            if fused is not None:
+                out['roofline_other']['conv3x3_conv1x1'] = fused
+            if a.layer_report:
+                layer_report(ex, per_op, a.layer_report)
+            if world == 1 and not a.no_alt_math:
+                out['alt_math'] = alt_math_leg(wl, dev, x, ims, min(a.steps, 30), ex.math, depth)
+                if ex.math != 'fp32' and 'fp32' in out['alt_math']:
+                    # `value` computes every product from 2-term fp16 splits (3 MFMA products, ~22-bit operands, fp32 accumulate);
+                    # this is the same step with every convolution on the exact-fp32 MFMA, v_mfma_f32_32x32x2_f32
+                    out['value_fp32_exact'] = out['alt_math']['fp32']
+                    out['value_fp32_exact_note'] = ('same loop, every convolution on the exact-fp32 MFMA (PPYOLO_HIP_MATH=fp32): %.2f of the '
+                                                    '157.3 TFLOP/s fp32-MFMA bound' % (out['alt_math']['fp32'] * total_flops / a.batch / 1e12 / FP32_MFMA_PEAK_TFLOPS))
+            if world == 1 and not a.no_host_input:
+                out['host_input'] = host_input_leg(ex, x, ims, min(a.steps, 30), lanes)
+            if world == 1 and not a.no_host_input:
+                out['roofline_other']['preprocess'] = preprocess_leg(cfg, wl['size'], a.batch, lanes, min(a.steps, 30),
+                                                                     not a.no_cpu_baseline)
+            if world == 1 and not a.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline(sd, cfg, wl['size'], a.batch)
+            if world == 1:
+                try:
+                    pn = parity_note_leg(model, wl, a.batch, x)
+                except Exception as exc:          # (a diagnostic field must not take the benchmark line with it)
+                    pn = dict(error='%s: %s' % (type(exc).__name__, exc))
+                if pn is not None:
+                    out['parity_note'] = pn
+            if world == 1 and not a.no_worst_case:
+                out['worst_case_regime'] = worst_case_leg(wl, dev, x, ims, sd, cfg, depth, min(a.min_seconds, 1.0) or 0.2,
+                                                          out['cpu_baseline']['cores'] if 'cpu_baseline' in out else 0)
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

@@ -3,7 +3,7 @@
 VAR=$1; VALS=$2; ROUNDS=${3:-2}; shift 3
 for r in $(seq 1 $ROUNDS); do
   for v in $VALS; do
-    env $VAR=$v python bench.py --no-cpu-baseline --no-alt-math --no-host-input --no-worst-case "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --no-cpu-baseline --no-alt-math --no-host-input --no-worst-case "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 r=d['roofline']

@@ -8,7 +8,7 @@ for i in 1 2 3; do
   for V in base "$@"; do
     if [ $V = base ]; then unset PPYOLO_HIP_TUNE_CACHE; else export PPYOLO_HIP_TUNE_CACHE=$V; fi
     for L in 2 1; do
-      python bench.py --in-flight $L --no-cpu-baseline --no-alt-math --no-host-input ${BENCH_ARGS} 2>/dev/null | python -c "
+      python bench.py --full --in-flight $L --no-cpu-baseline --no-alt-math --no-host-input ${BENCH_ARGS} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$V lanes=$L run $i: %.1f img/s  frac %.4f' % (d['value'], d['roofline']['frac']))" >> $OUT
