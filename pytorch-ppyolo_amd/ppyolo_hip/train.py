@@ -68,6 +68,22 @@ def _r32(c):
     return (c + 31) // 32 * 32
 
 
+def train_fwd_cfg(cfg_id, splitk):
+    """(tile configuration, split-K) a table names for a forward convolution -> the pair the training forward launches.  The
+    training tables fall back on the inference tables' entries, whose ids include families that cannot give the BatchNorm
+    statistics this forward takes from the epilogue:
+      * a k-parity tile (ws + 9 .. ws + 15, round 6): the same tile with one consumer group, split-K kept;
+      * a wave-private small-output tile (small_first_cfg() and up): its split-K counts k-parts inside the workgroup, not
+        workspace splits, and it writes no statistics -- the library's own choice instead, (-1, 0).
+    Data gradients keep the table's ids: they take no statistics, and every family runs them (tests/test_gpu_train_replay.py)."""
+    ws0 = K.ws_first_cfg()
+    if ws0 + 9 <= cfg_id < ws0 + 16:
+        return ws0 + (0, 1, 2, 3, 1, 2, 3)[cfg_id - ws0 - 9], splitk
+    if cfg_id >= K.small_first_cfg():
+        return -1, 0
+    return cfg_id, splitk
+
+
 class ModelSettings(object):
     """What the training step reads from a configuration object (config/ppyolo_2x.py), taken from the MODEL instead -- as the
     reference's train.py builds it: backbone(**cfg.backbone), YOLOv3Head(yolo_loss=YOLOv3Loss(iou_loss=..., ...), ...)."""
@@ -461,12 +477,7 @@ class TrainStep(object):
                             w_x3=None if (use_f16 or self.fp32) else self._planes(ent), w_f16=ent['f16'] if use_f16 else None,
                             amax_in=xin.amax if use_f16 else None)
         key = 'conv:N%d:H%d:W%d:C%d:K%d:R%d:s%d' % (xin.N, xin.H, xin.W, Cp, Kout, R, stride)
-        cfg_id, splitk = (-1, 0) if self.fp32 else self._choose(key, run, R * S * Cp // 32, use_f16)
-        kp0 = K.ws_first_cfg() + 9
-        if kp0 <= cfg_id < kp0 + 7:
-            # a k-parity tile (round 6; the inference table's entry for this geometry -- the training tables fall back on it): those
-            # kernels do not emit the BatchNorm statistics this forward takes from the epilogue; the same tile with one consumer group
-            cfg_id = K.ws_first_cfg() + (0, 1, 2, 3, 1, 2, 3)[cfg_id - kp0]
+        cfg_id, splitk = (-1, 0) if self.fp32 else train_fwd_cfg(*self._choose(key, run, R * S * Cp // 32, use_f16))
         # BatchNorm statistics from the convolution's epilogue (the f16x2 kernels, one split): saves the
         # statistics kernel's pass over the raw output
         slices = 0
