@@ -392,6 +392,25 @@ int ppy_preprocess_u8_f32(int n, const unsigned char *const *images, const int *
                           const int *row_stride, int swap_rb, int S, const float *lut /* device [3][256] */,
                           float *out, void *stream);
 
+/* Training batches (ppyolo_hip/augment.py TrainBatchBuilder): the reference's training reader (train.py:36-152) with
+ * the transforms of config/ppyolo_2x.py:154-251, planned on the host.  blob: DEVICE copy of the planner's upload (8-byte
+ * aligned, blob_bytes long): n per-sample descriptors (augment.hip struct AugSample, 328 bytes each) at offset 0, then
+ * the tables, uint8 BGR sources, target offsets / values and boxes they point to by byte offset.  Descriptors whose
+ * offsets or extents fall outside the blob are skipped (their output is left as it was).
+ * render: every output pixel of every sample = cv2.resize (the sample's interpolation, fx = S / w, fy = S / h) of the
+ * pre-resize image, NormalizeImage (uint8 canvas: lut[c][v], device [3][256]; float canvas: mean_std = HOST
+ * {mean[3], std[3]} with is_scale), CHW -> out device [n][3][S][S] float32. */
+int ppy_augment_render_f32(const void *blob, long long blob_bytes, int n, int S, const float *lut,
+                           const double *mean_std, int is_scale, float *out, void *stream);
+/* The pre-resize image of sample `index` into out (device [h][w][3] of dtype 0 uint8 / 1 float32 / 2 float64: the
+ * sample's canvas dtype); h, w, dtype must match the descriptor, otherwise nothing is written.  For pinning. */
+int ppy_augment_canvas(const void *blob, long long blob_bytes, int index, int h, int w, int dtype, void *out,
+                       void *stream);
+/* Dense YOLO targets: out (device float32, total elements, 16-byte aligned) is zero-filled, then out[offsets[i]] =
+ * values[i] for the n host-computed elements (device arrays, offsets unique; targets.gt2yolo_records). */
+int ppy_augment_targets_f32(float *out, long long total, const long long *offsets, const float *values, int n,
+                            void *stream);
+
 /* torch.nn.MaxPool2d(3, 2, 1) of the stem (reference model/resnet_vd.py:103, :136). */
 int ppy_maxpool3x3s2_f32(const float *x, int x_ld, float *y, int y_ld, int N, int H, int W,
                          int C, void *stream);

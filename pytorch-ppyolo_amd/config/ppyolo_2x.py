@@ -3,8 +3,8 @@
 Data-only mirror of the reference's `config/ppyolo_2x.py:13-234` (class
 `PPYOLO_2x_Config`): only the attributes the inference hot path reads are kept
 (`backbone_type/backbone`, `head_type/head`, `nms_cfg`, `eval_cfg/test_cfg`,
-`num_classes`).  Training / data-augmentation attributes are out of scope
-(SURVEY.md section 8f).
+`num_classes`), plus the training reader's transform settings that
+`ppyolo_hip.augment.TrainBatchBuilder` reads (`_train_transforms`).
 """
 
 _COCO_ANCHORS_9 = [[10, 13], [16, 30], [33, 23], [30, 61], [62, 45],
@@ -15,6 +15,26 @@ def _matrix_nms_defaults():
     # reference: config/ppyolo_2x.py:143-151
     return dict(nms_type='matrix_nms', score_threshold=0.01, post_threshold=0.01,
                 nms_top_k=500, keep_top_k=100, use_gaussian=False, gaussian_sigma=2.)
+
+
+def _train_transforms(cfg, gt2yolo):
+    """The reference's training-reader settings (config/ppyolo_2x.py:154-251; ppyolo_r18vd.py differs in
+    gt2YoloTarget only), consumed by ppyolo_hip.augment.TrainBatchBuilder.  `context` is left as the
+    inference harness has it: the builder carries its own field list."""
+    cfg.decodeImage.update(with_mixup=True, with_cutmix=False)
+    cfg.mixupImage = dict(alpha=1.5, beta=1.5)
+    cfg.colorDistort = dict()
+    cfg.randomExpand = dict(fill_value=[123.675, 116.28, 103.53])
+    cfg.randomCrop = dict()
+    cfg.randomFlipImage = dict(is_normalized=False)
+    cfg.normalizeBox = dict()
+    cfg.padBox = dict(num_max_boxes=50)
+    cfg.bboxXYXY2XYWH = dict()
+    cfg.randomShape = dict(sizes=[320, 352, 384, 416, 448, 480, 512, 544, 576, 608], random_inter=True)
+    cfg.gt2YoloTarget = gt2yolo
+    cfg.sample_transforms_seq = ['decodeImage', 'mixupImage', 'colorDistort', 'randomExpand', 'randomCrop',
+                                 'randomFlipImage', 'normalizeBox', 'padBox', 'bboxXYXY2XYWH']
+    cfg.batch_transforms_seq = ['randomShape', 'normalizeImage', 'permute', 'gt2YoloTarget']
 
 
 class PPYOLO_2x_Config(object):
@@ -58,3 +78,5 @@ class PPYOLO_2x_Config(object):
                                    is_scale=True, is_channel_first=False)
         self.permute = dict(to_bgr=False, channel_first=True)
         self.resizeImage = dict(target_size=608, interp=2)
+        _train_transforms(self, dict(anchor_masks=[[6, 7, 8], [3, 4, 5], [0, 1, 2]], anchors=[list(a) for a in _COCO_ANCHORS_9],
+                                     downsample_ratios=[32, 16, 8], num_classes=self.num_classes))

@@ -2,7 +2,7 @@
 hyper-parameters.  Data-only mirror of the reference's
 `config/ppyolo_r18vd.py:13-226` (`PPYOLO_r18vd_Config`), inference attributes only.
 """
-from .ppyolo_2x import _matrix_nms_defaults
+from .ppyolo_2x import _matrix_nms_defaults, _train_transforms
 
 
 class PPYOLO_r18vd_Config(object):
@@ -43,3 +43,6 @@ class PPYOLO_r18vd_Config(object):
                                    is_scale=True, is_channel_first=False)
         self.permute = dict(to_bgr=False, channel_first=True)
         self.resizeImage = dict(target_size=416, interp=2)
+        _train_transforms(self, dict(anchor_masks=[[3, 4, 5], [0, 1, 2]],
+                                     anchors=[[10, 14], [23, 27], [37, 58], [81, 82], [135, 169], [344, 319]],
+                                     downsample_ratios=[32, 16], num_classes=self.num_classes))

@@ -91,6 +91,10 @@ _PROTOS = {
                                                 c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ppy_preprocess_u8_f32': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p]),
+    'ppy_augment_render_f32': (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int, c_void_p,
+                                        c_void_p]),
+    'ppy_augment_canvas': (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ppy_augment_targets_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p]),
     'ppy_maxpool3x3s2_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ppy_avgpool2x2_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ppy_spp_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,

@@ -537,6 +537,37 @@ def preprocess_images(images_u8, target_size, lut, out, swap_rb=True):
         int(bool(swap_rb)), int(target_size), lut.data_ptr(), out.data_ptr(), _stream()), 'ppy_preprocess_u8_f32')
 
 
+def augment_render(blob, n, S, lut, mean, std, out, is_scale=True):
+    """TrainBatchBuilder's render launch: blob = device uint8 copy of augment.pack_batch (descriptors at offset 0) ->
+    out [n,3,S,S] float32."""
+    _dev(blob, lut, out)
+    assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.data_ptr() % 8 == 0
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, S, S)
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (3, 256)
+    ms = (ctypes.c_double * 6)(*[float(v) for v in list(mean) + list(std)])
+    check(lib().ppy_augment_render_f32(blob.data_ptr(), blob.numel(), int(n), int(S), lut.data_ptr(), ms, int(bool(is_scale)),
+                                       out.data_ptr(), _stream()), 'ppy_augment_render_f32')
+
+
+def augment_canvas(blob, index, out):
+    """The pre-resize image of sample `index` of a packed blob -> out [h,w,3] uint8 / float32 / float64 (its canvas dtype)."""
+    _dev(blob, out)
+    assert blob.dtype == torch.uint8 and blob.is_contiguous() and out.is_contiguous() and out.dim() == 3 and out.shape[2] == 3
+    dt = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}[out.dtype]
+    check(lib().ppy_augment_canvas(blob.data_ptr(), blob.numel(), int(index), out.shape[0], out.shape[1], dt, out.data_ptr(),
+                                   _stream()), 'ppy_augment_canvas')
+
+
+def augment_targets(flat, blob, off_pos, val_pos, n):
+    """Zero-fill `flat` (device float32) and write the n (offset, value) target elements stored in `blob` at byte
+    offsets off_pos (int64) / val_pos (float32)."""
+    _dev(flat, blob)
+    assert flat.dtype == torch.float32 and flat.is_contiguous() and off_pos % 8 == 0 and val_pos % 4 == 0
+    base = blob.data_ptr()
+    check(lib().ppy_augment_targets_f32(flat.data_ptr(), flat.numel(), base + off_pos if n else None, base + val_pos if n else None,
+                                        int(n), _stream()), 'ppy_augment_targets_f32')
+
+
 def maxpool3x3s2(x, y):
     _dev(x.t, y.t)
     check(lib().ppy_maxpool3x3s2_f32(x.ptr, x.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C, _stream()), 'ppy_maxpool3x3s2_f32')

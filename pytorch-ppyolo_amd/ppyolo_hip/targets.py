@@ -70,6 +70,55 @@ def gt2yolo_target(gt_bbox, gt_class, gt_score, anchors, anchor_masks, downsampl
     return out
 
 
+def gt2yolo_records(gt_bbox, gt_class, gt_score, anchors, anchor_masks, downsample_ratios, num_classes, image_size, iou_thresh=1.):
+    """The non-zero elements of gt2yolo_target's levels, laid out back to back in ONE flat float32 buffer (level 0 first,
+    each [N, len(mask), 6 + C, grid, grid]) -> (offsets int64 [E], values float32 [E]), offsets unique and ascending.  Same
+    arithmetic and the same collision rule: where boxes share an (anchor, cell) the later box's fields win and every box's
+    class element stays set (csrc/augment.hip writes them over a zero fill)."""
+    gt_bbox = np.asarray(gt_bbox, dtype=np.float32)
+    gt_class, gt_score = np.asarray(gt_class), np.asarray(gt_score, dtype=np.float32)
+    N, G = gt_bbox.shape[:2]
+    size = int(image_size)
+    an = np.asarray(anchors)
+    an_hw = an / np.array([[size, size]])
+    img, box = np.nonzero((gt_bbox[..., 2] > 0.) & (gt_bbox[..., 3] > 0.) & (gt_score > 0.))
+    gx, gy, gw, gh = (gt_bbox[img, box, k] for k in range(4))
+    cls, score = gt_class[img, box].astype(np.int64), gt_score[img, box]
+    iou = _wh_iou_all(gw, gh, an_hw)
+    best = np.where(iou.max(axis=1) > 0., iou.argmax(axis=1), -1)
+    f32 = np.float32
+    offs, vals = [], []
+    base = 0
+    for mask, ds in zip(anchor_masks, downsample_ratios):
+        grid = int(size / ds)
+        A, F, plane = len(mask), 6 + num_classes, grid * grid
+        gi, gj = (gx * f32(grid)).astype(np.int64), (gy * f32(grid)).astype(np.int64)
+        for k, a_idx in enumerate(mask):
+            sel = best == a_idx
+            if iou_thresh < 1:
+                sel = sel | ((best != a_idx) & (iou[:, a_idx] > iou_thresh))
+            rows = np.nonzero(sel)[0]
+            if not rows.size:
+                continue
+            n_, j_, i_ = img[rows], gj[rows], gi[rows]
+            cell = base + (n_ * A + k) * F * plane + j_ * grid + i_          # element of field 0
+            fields = [gx[rows] * f32(grid) - gi[rows].astype(f32), gy[rows] * f32(grid) - gj[rows].astype(f32),
+                      np.log(gw[rows] * f32(size) / f32(an[a_idx][0])), np.log(gh[rows] * f32(size) / f32(an[a_idx][1])),
+                      f32(2.0) - gw[rows] * gh[rows], score[rows]]
+            for f, v in enumerate(fields):
+                offs.append(cell + f * plane)
+                vals.append(np.asarray(v, np.float32))
+            offs.append(cell + (6 + cls[rows]) * plane)
+            vals.append(np.ones(rows.size, np.float32))
+        base += N * A * F * plane
+    if not offs:
+        return np.zeros(0, np.int64), np.zeros(0, np.float32)
+    offs, vals = np.concatenate(offs), np.concatenate(vals)
+    # the last write of each element wins: keep the last occurrence (rows are in (image, box) order within an element)
+    rev_u, rev_i = np.unique(offs[::-1], return_index=True)
+    return rev_u.astype(np.int64), vals[::-1][rev_i]
+
+
 def synth_ground_truth(N, seed, max_boxes=50):
     """Deterministic synthetic ground truth in the reader's format (bench / smoke: there is no dataset here)."""
     rng = np.random.RandomState(seed)

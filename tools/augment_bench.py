@@ -1,0 +1,131 @@
+"""Training-batch builder timings (ppyolo_hip/augment.py, csrc/augment.hip).
+
+    python tools/augment_bench.py [--bs 8] [--iters 20]
+
+Reports: host plan time per batch (the reference's transforms, draw for draw, no pixel work); device time of the render
+and target kernels (HIP events) at bs 8 for S = 320 and 608 and every interpolation, on 640 x 480 sources through the
+full chain (mixup partners, colour ops, expand, crop, flip as drawn); the builder feeding TrainStep.step (steps/s, builder
+on a producer thread one batch ahead)."""
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'pytorch-ppyolo_amd')]
+
+from config import PPYOLO_2x_Config  # noqa: E402
+from ppyolo_hip import augment as A, ops, targets as T  # noqa: E402
+
+
+def samples(rng, n, hw=(480, 640)):
+    out = []
+    for k in range(n):
+        def one():
+            G = int(rng.randint(1, 20))
+            h, w = hw
+            x1, y1 = rng.uniform(0, w - 60, G), rng.uniform(0, h - 60, G)
+            box = np.stack([x1, y1, x1 + rng.uniform(20, 60, G), y1 + rng.uniform(20, 60, G)], 1).astype(np.float32)
+            return dict(image=rng.randint(0, 256, (h, w, 3)).astype(np.uint8), h=h, w=w, gt_bbox=box,
+                        gt_class=rng.randint(0, 80, (G, 1)).astype(np.int32), gt_score=np.ones((G, 1), np.float32),
+                        is_crowd=np.zeros((G, 1), np.int32))
+        s = one()
+        s['mixup'] = one()
+        out.append(s)
+    return out
+
+
+def ev_time(fn, iters):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fn()
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--bs', type=int, default=8)
+    ap.add_argument('--iters', type=int, default=20)
+    ap.add_argument('--train-steps', type=int, default=20)
+    a = ap.parse_args()
+    cfg = PPYOLO_2x_Config()
+    b = A.TrainBatchBuilder(cfg)
+    rng = np.random.RandomState(0)
+    batch = samples(rng, a.bs)
+    res = dict(bs=a.bs)
+    t0 = time.perf_counter()
+    for i in range(a.iters):
+        b.plan(batch, 608, np.random.RandomState(i))
+    res['plan_ms'] = (time.perf_counter() - t0) * 1e3 / a.iters
+    lut = torch.from_numpy(b.lut_np).cuda()
+    res['render_ms'], res['targets_ms'] = {}, {}
+    for S in (320, 608):
+        for interp in A.INTERPS:
+            b.random_inter = False
+            recipes, bb, cl, sc = b.plan(batch, S, np.random.RandomState(1))
+            for r in recipes:           # force the interpolation, keep the drawn chain
+                r['interp'] = interp
+                r['resize'] = A.resize_plan(r['crop'][2], r['crop'][3], r['fx'], r['fy'], interp, r['canvas_dtype'])
+            o, v = T.gt2yolo_records(bb, cl, sc, b.anchors, b.anchor_masks, b.downsample_ratios, 80, S)
+            blob, lay = A.pack_batch(recipes, True, o, v, bb, cl, sc)
+            dev = torch.from_numpy(blob).cuda()
+            out = torch.empty((a.bs, 3, S, S), device='cuda')
+            res['render_ms']['%d_%d' % (S, interp)] = ev_time(
+                lambda: ops.augment_render(dev, a.bs, S, lut, b.mean, b.std, out), a.iters)
+            if interp == A.INTERPS[0]:
+                total = sum(a.bs * len(m) * 86 * (S // d) ** 2 for m, d in zip(b.anchor_masks, b.downsample_ratios))
+                flat = torch.empty(total, device='cuda')
+                res['targets_ms'][str(S)] = ev_time(lambda: ops.augment_targets(flat, dev, lay['toff'], lay['tval'], len(o)), a.iters)
+    b.random_inter = True
+    # the builder feeding the training step, one batch ahead on a producer thread
+    try:
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        from conftest import build_model
+        from ppyolo_hip.train import TrainStep
+        model, _ = build_model(cfg, 0, 'cuda')
+        ts = TrainStep(model, cfg)
+        S = 608
+        side = torch.cuda.Stream()
+        q = []
+        ready = threading.Semaphore(0)
+
+        def produce(i):
+            with torch.cuda.stream(side):
+                d = b(batch, S, np.random.RandomState(100 + i))
+                e = torch.cuda.Event()
+                e.record(side)
+            q.append((d, e))
+            ready.release()
+        th = threading.Thread(target=produce, args=(0,))
+        th.start()
+        for it in range(a.train_steps + 2):
+            if it == 2:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+            ready.acquire()
+            th.join()
+            d, e = q.pop(0)
+            th = threading.Thread(target=produce, args=(it + 1,))
+            th.start()
+            torch.cuda.current_stream().wait_event(e)
+            ts.step(d['images'], d['gt_bbox'], [d['target0'], d['target1'], d['target2']], 1e-4)
+        torch.cuda.synchronize()
+        res['train_steps_per_s'] = a.train_steps / (time.perf_counter() - t0)
+        th.join()
+    except Exception as ex:          # report, do not hide
+        res['train_error'] = repr(ex)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

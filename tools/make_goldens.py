@@ -919,8 +919,134 @@ def g18_headline_sizes():
         save('g18_' + tag, **arrs)
 
 
+def g19_augment():
+    """The reference's training reader (train.py:36-60 multi_thread_op with num_threads = 1, the transforms of
+    config/ppyolo_2x.py:154-251) run by its own classes on seeded batches of small synthetic samples.  cv2 is a stub:
+    imdecode / cvtColor of raw arrays, and a resize that RECORDS (canvas, fx, fy, interp) -- the resize itself is unpinned.
+    Recorded per sample: inputs, pre-resize canvas in its native dtype, draws, final boxes; per batch: seed, shape and
+    np.random's state after the batch; NormalizeImage + Permute of the reference applied to each float canvas."""
+    import types
+    rec = []
+    stub = types.ModuleType('cv2')
+    for i, k in enumerate(('INTER_NEAREST', 'INTER_LINEAR', 'INTER_CUBIC', 'INTER_AREA', 'INTER_LANCZOS4')):
+        setattr(stub, k, i)
+    stub.COLOR_BGR2RGB = 4
+    stub.imdecode = lambda data, flag: data[8:].reshape(int(data[:4].view(np.int32)[0]), int(data[4:8].view(np.int32)[0]), 3).copy()
+    stub.cvtColor = lambda im, code: np.ascontiguousarray(im[:, :, ::-1])
+
+    def _resize(im, dsize, _a, fx, fy, interpolation):
+        rec.append((im.copy(), fx, fy, interpolation))
+        return np.zeros((int(round(im.shape[0] * fy)), int(round(im.shape[1] * fx)), 3), im.dtype)
+    stub.resize = _resize
+    saved = sys.modules.get('cv2')
+    sys.modules['cv2'] = stub
+    try:
+        tr = _load('ref_transform_g19', os.path.join(REF, 'tools', 'transform.py'))
+    finally:
+        if saved is None:
+            del sys.modules['cv2']
+        else:
+            sys.modules['cv2'] = saved
+    tr.cv2 = stub
+    cfg = PPYOLO_2x_Config()
+    ctx = cfg.context
+    st = [tr.DecodeImage(**cfg.decodeImage), tr.MixupImage(**cfg.mixupImage), tr.ColorDistort(**cfg.colorDistort),
+          tr.RandomExpand(**cfg.randomExpand), tr.RandomCrop(**cfg.randomCrop), tr.RandomFlipImage(**cfg.randomFlipImage),
+          tr.NormalizeBox(**cfg.normalizeBox), tr.PadBox(**cfg.padBox), tr.BboxXYXY2XYWH(**cfg.bboxXYXY2XYWH)]
+    bt = [tr.RandomShapeSingle(random_inter=cfg.randomShape['random_inter']), tr.NormalizeImage(**cfg.normalizeImage),
+          tr.Permute(**cfg.permute), tr.Gt2YoloTargetSingle(**cfg.gt2YoloTarget)]
+    norm, perm = tr.NormalizeImage(**cfg.normalizeImage), tr.Permute(**cfg.permute)
+
+    def src(g, n_box):
+        h, w = int(g.randint(20, 53)), int(g.randint(20, 53))
+        img = g.randint(0, 256, size=(h, w, 3)).astype(np.uint8)
+        x1, y1 = g.uniform(0, w - 6, n_box), g.uniform(0, h - 6, n_box)
+        box = np.stack([x1, y1, x1 + g.uniform(3, w - x1), y1 + g.uniform(3, h - y1)], 1).astype(np.float32)
+        box[:, 2] = np.minimum(box[:, 2], w - 1)
+        box[:, 3] = np.minimum(box[:, 3], h - 1)
+        return dict(img=img, gt_bbox=box, gt_class=g.randint(0, 80, (n_box, 1)).astype(np.int32),
+                    gt_score=np.ones((n_box, 1), np.float32), is_crowd=np.zeros((n_box, 1), np.int32))
+
+    def encoded(img):
+        return np.concatenate([np.array(img.shape[:2], np.int32).view(np.uint8), img.reshape(-1)]).tobytes()
+
+    arrs = {}
+    cover = set()
+    nb, bs = 0, 4
+    for seed in range(1000):
+        g = np.random.RandomState(1000 + seed)
+        samples, srcs = [], []
+        for k in range(bs):
+            a = src(g, int(g.choice([0, 1, 3, 8, 30, 55])))
+            b = src(g, int(g.choice([0, 2, 5, 30]))) if g.rand() < 0.7 else None
+            srcs.append((a, b))
+            smp = dict(image=encoded(a['img']), h=a['img'].shape[0], w=a['img'].shape[1],
+                       **{k2: a[k2].copy() for k2 in ('gt_bbox', 'gt_class', 'gt_score', 'is_crowd')})
+            if b is not None:
+                smp['mixup'] = dict(image=encoded(b['img']), h=b['img'].shape[0], w=b['img'].shape[1],
+                                    **{k2: b[k2].copy() for k2 in ('gt_bbox', 'gt_class', 'gt_score', 'is_crowd')})
+            samples.append(smp)
+        np.random.seed(seed)
+        shape = np.random.choice(cfg.randomShape['sizes'])
+        del rec[:]
+        outs = []
+        for smp in samples:                       # multi_thread_op, num_threads = 1
+            s = smp
+            for t in st:
+                s = t(s, ctx)
+            for t in bt:
+                s = t(shape, s, ctx) if isinstance(t, tr.RandomShapeSingle) else t(s, ctx)
+            outs.append(s)
+        state = np.random.get_state()
+        new = set()
+        for k, ((a, b), (cv, fx, fy, interp), s) in enumerate(zip(srcs, rec, outs)):
+            new.add(('interp', int(interp)))
+            new.add(('dtype', str(cv.dtype)))
+            if b is not None and (b['img'].shape[0] > a['img'].shape[0]) != (b['img'].shape[1] > a['img'].shape[1]):
+                new.add('mixup_larger_one_dim')
+            if len(a['gt_bbox']) + (len(b['gt_bbox']) if b is not None else 0) > 50:
+                new.add('over_50')
+        # which branches the batch took: replay the draws with the planner-free reference objects is not possible here;
+        # the interp / dtype coverage is recorded, the rest is checked by tests/test_augment_plan.py through the planner
+        if nb < 10 or not new <= cover:
+            cover |= new
+            p = 'b%d_' % nb
+            arrs[p + 'seed'] = np.array(seed)
+            arrs[p + 'shape'] = np.array(int(shape))
+            arrs[p + 'state_keys'] = state[1]
+            arrs[p + 'state_pos'] = np.array(state[2:4], dtype=np.float64)
+            arrs[p + 'state_gauss'] = np.array(state[4])
+            for k, ((a, b), (cv, fx, fy, interp), s) in enumerate(zip(srcs, rec, outs)):
+                q = p + 's%d_' % k
+                for nm, r in (('a', a), ('b', b)):
+                    if r is None:
+                        continue
+                    for k2 in ('img', 'gt_bbox', 'gt_class', 'gt_score', 'is_crowd'):
+                        arrs[q + nm + '_' + k2] = r[k2]
+                arrs[q + 'canvas'] = cv
+                arrs[q + 'draws'] = np.array([fx, fy, interp], np.float64)
+                for k2 in ('gt_bbox', 'gt_class', 'gt_score'):
+                    arrs[q + 'out_' + k2] = s[k2]
+                if cv.dtype != np.uint8:
+                    arrs[q + 'normalized'] = perm(norm({'image': cv.copy()}, None), None)['image']
+            nb += 1
+        want = {('interp', i) for i in range(5)} | {('dtype', d) for d in ('uint8', 'float32', 'float64')} | {'mixup_larger_one_dim', 'over_50'}
+        if want <= cover and nb >= 12:
+            break
+    assert want <= cover, want - cover
+    arrs['n_batches'] = np.array(nb)
+    arrs['batch_size'] = np.array(bs)
+    for k in ('mixupImage', 'colorDistort', 'randomExpand', 'randomCrop', 'randomFlipImage', 'normalizeBox', 'padBox',
+              'bboxXYXY2XYWH', 'randomShape', 'gt2YoloTarget', 'decodeImage'):
+        arrs['cfg_2x_' + k] = np.array(repr(sorted(getattr(cfg, k).items())))
+    arrs['cfg_r18vd_gt2YoloTarget'] = np.array(repr(sorted(PPYOLO_r18vd_Config().gt2YoloTarget.items())))
+    arrs['cfg_sample_transforms_seq'] = np.array(cfg.sample_transforms_seq)
+    arrs['cfg_batch_transforms_seq'] = np.array(cfg.batch_transforms_seq)
+    save('g19_augment', **arrs)
+
+
 ALL = dict(g1=g1_conv_units, g2=g2_dcn, g3=g3_coord_spp, g4=g4_decode, g5=g5_matrix_nms, g67=g6_g7_models,
-           g8=g8_preprocess, g9=g9_decode_harness, g10=g10_coco_records, g11=g11_state_dict_layout, g12=g12_train_step, g13=g13_ema, g14=g14_train_loop, g15=g15_dcn_backward, g16=g16_train_step_backbone, g17=g17_paddle_names, g18=g18_headline_sizes)
+           g8=g8_preprocess, g9=g9_decode_harness, g10=g10_coco_records, g11=g11_state_dict_layout, g12=g12_train_step, g13=g13_ema, g14=g14_train_loop, g15=g15_dcn_backward, g16=g16_train_step_backbone, g17=g17_paddle_names, g18=g18_headline_sizes, g19=g19_augment)
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
