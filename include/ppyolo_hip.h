@@ -411,6 +411,38 @@ int ppy_augment_canvas(const void *blob, long long blob_bytes, int index, int h,
 int ppy_augment_targets_f32(float *out, long long total, const long long *offsets, const float *values, int n,
                             void *stream);
 
+/* COCO bbox evaluation (ppyolo_hip/cocoeval.py BboxEvaluator): what the reference's eval ends in, tools/cocotools.py:44-98
+ * bbox_eval -> cocoapi_eval -> pycocotools COCOeval(cocoGt, cocoDt, 'bbox').evaluate() + accumulate(), bit for bit in
+ * float64 (tests/cocoeval_ref.py restates it).  Records are 6 doubles (x, y, w, h, area, score) plus pair[i] = image index *
+ * num_cats + category index (-1: not a record); images and categories are indexed in sorted id order.
+ * records: forward_padded rows dets [n][keep_k][6] float32 (label, score, xmin, ymin, xmax, ymax) -> the reference writer's
+ * record arithmetic (cocotools.py:168-186: w = xmax - xmin + 1 in float32, each bbox entry round(double(v) * 10) / 10,
+ * score double(float32)), area = w * h (COCO.loadRes).  Rows at or beyond count[i] (device [n]) and rows whose class maps to
+ * no GT category (cls2cat: device [num_classes], class -> category index or -1) get pair -1; img_index: device [n].  A NaN in
+ * a record row sets *bad = 1 (device int).  records / pair: device [n * keep_k]. */
+int ppy_cocoeval_records_f32(const float *dets, int n, int keep_k, const int *count, const int *img_index,
+                             const int *cls2cat, int num_classes, int num_cats, double *records, int *pair, int *bad,
+                             void *stream);
+/* Workspace of ppy_cocoeval_bbox for these sizes (0 = invalid sizes). */
+size_t ppy_cocoeval_workspace_bytes(long long num_records, int num_images, int num_cats, int num_gts, int num_iou_thrs,
+                                    int num_areas, int num_max_dets);
+/* evaluate() + accumulate() over num_records records.  GTs grouped per pair in annotation-file order: gt_off [P + 1] (P =
+ * num_images * num_cats), gt_box [G][4] (x, y, w, h), gt_area [G] (the annotation's `area`), gt_crowd [G], gt_idnz [G]
+ * (annotation id != 0: pycocotools reads a match to id 0 as none), gt_cat_off [num_cats + 1] (GTs per category, prefix).
+ * iou_row_gts: the largest GT count of a pair (at most 4096 are used): a pair's IoU row with one detection is kept in that
+ * much dynamic LDS; pairs with more GTs recompute their IoUs per chain, with the same bits.
+ * Params as device doubles from numpy (iou_thrs [T], rec_thrs [R], area_rng [A][2], inclusive bounds), max_dets [M] on the
+ * device and h_max_dets the same values on the host (the last one truncates each pair's list); A * T <= 64.  Outputs in
+ * COCOeval.eval's layout: precision / scores [T][R][num_cats][A][M], recall [T][num_cats][A][M], -1 where pycocotools
+ * leaves -1.  Repeatable bit for bit: sorts on unique keys, no atomics. */
+int ppy_cocoeval_bbox(const double *records, const int *pair, long long num_records, int num_images, int num_cats,
+                      const int *gt_off, const double *gt_box, const double *gt_area, const int *gt_crowd,
+                      const int *gt_idnz, const int *gt_cat_off, int num_gts, int iou_row_gts,
+                      const double *iou_thrs, int T,
+                      const double *rec_thrs, int R, const double *area_rng, int A, const int *max_dets,
+                      const int *h_max_dets, int M, double *precision, double *recall, double *scores, void *workspace,
+                      size_t workspace_bytes, void *stream);
+
 /* torch.nn.MaxPool2d(3, 2, 1) of the stem (reference model/resnet_vd.py:103, :136). */
 int ppy_maxpool3x3s2_f32(const float *x, int x_ld, float *y, int y_ld, int N, int H, int W,
                          int C, void *stream);

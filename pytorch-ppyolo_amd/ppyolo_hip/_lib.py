@@ -95,6 +95,12 @@ _PROTOS = {
                                         c_void_p]),
     'ppy_augment_canvas': (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ppy_augment_targets_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p]),
+    'ppy_cocoeval_workspace_bytes': (c_size_t, [c_longlong] + [c_int] * 6),
+    'ppy_cocoeval_records_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+    'ppy_cocoeval_bbox': (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_void_p, c_int, c_void_p,
+                                  c_int, c_void_p, c_int, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_size_t, c_void_p]),
     'ppy_maxpool3x3s2_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ppy_avgpool2x2_f32': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     'ppy_spp_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
