@@ -129,21 +129,36 @@ int ppy_conv2d_bn_act_split_f32(const float *x, int x_ld, const float *w_krsc, c
 size_t ppy_conv2d_workspace_bytes(int N, int H, int W, int C, int K, int R, int S, int stride,
                                   int pad, int cfg, int splitk);
 int ppy_conv2d_num_configs(void);
-/* Map of the cfg ids (all families compute the same operator; the f16x2 families are bit-identical to each other):
- *   0-30   exact-fp32 MFMA tiles (csrc/conv_igemm.hip)            31-39  bf16x3 tiles (csrc/conv_x3.hip; need w_x3)
- *   40-66  f16x2 tiles, 9 shapes x {2, 3, 4} LDS stages           67-84  the same with slab reuse (3x3 / stride 1 / pad 1 only)
- *   85-93  f16x2 tiles of 96 / 192 rows x {2, 3, 4} stages        then, from the functions below:
- *   stream_first + {0, 1}   streaming 1x1 kernel (C = 64 / 128)   patch_first   patch kernel of the 3x3 stem layers (C = 32)
- *   ws_first + {0..15}      f16x2 tiles with specialised waves: 128x128 (3 / 4 stages), 64x128 (4 / 6), the three PRE variants,
- *                           256x128 with eight consumer waves (2 / 3 stages); round 6: + 9 / + 10 = 128x128 (3 / 4 stages), + 11 / + 12 = 64x128 (4 / 6 stages), + 13 = 128x128 and + 14 / + 15 = 64x128 with two
- *                           32-deep chunks per stage (one barrier per 64), all with eight
- *                           consumer waves as two "k-parity" groups (group g multiplies k-step g of every 32-deep chunk; the two
- *                           sums are added at the end -- one more fp32 rounding, so these seven are bit-identical to each other, not
- *                           to the other f16x2 tiles)
- *   small_first + {0..3}    wave-private tiles for small outputs (ppy_conv2d_small_first_config below)
+/* The cfg ids, family by family in id order (all families compute the same operator; the f16x2 families are bit-identical to
+ * each other, the seven k-parity tiles to one another):  exact-fp32 MFMA tiles (csrc/conv_igemm.hip), bf16x3 tiles and f16x2 tiles --
+ * plain, with slab reuse (3x3 / stride 1 / pad 1 only), with 96 / 192 rows -- (csrc/conv_x3.hip), the streaming 1x1 kernel
+ * (csrc/conv_stream.hip), the patch kernel of the 3x3 stem layers (csrc/conv_patch.hip), the f16x2 tiles with specialised waves --
+ * plain, PRE, k-parity -- (csrc/conv_ws.hip), the wave-private tiles for small outputs (csrc/conv_small.hip).  What one id is and
+ * can do is answered by ppy_conv2d_config_info, filled in by the family that dispatches the id.
  * An explicit id on a geometry its kernel does not cover returns PPY_ERR_BAD_ARG (never a silent other kernel); the one exception:
- * the scalar epilogue (K % 4 != 0 or unaligned rows) does not exist for the wave tiles of six / eight 32x32 blocks (40, 46, 85-93
- * and their deeper variants) -- such a launch runs on the exact-fp32 fall-back tile. */
+ * the scalar epilogue (K % 4 != 0 or unaligned rows) does not exist for the wave tiles of six / eight 32x32 blocks -- such a launch
+ * runs on the exact-fp32 fall-back tile. */
+enum { PPY_CFG_FP32 = 0, PPY_CFG_BF16X3, PPY_CFG_F16X2, PPY_CFG_F16X2_SLAB, PPY_CFG_F16X2_TALL, PPY_CFG_STREAM, PPY_CFG_PATCH,
+       PPY_CFG_WS, PPY_CFG_WS_PRE, PPY_CFG_WS_KPARITY, PPY_CFG_SMALL };                       /* ppy_conv_cfg_info.family */
+enum { PPY_CFG_OPERANDS_FP32 = 0,      /* the fp32 weights only */
+       PPY_CFG_OPERANDS_BF16X3,        /* + w_x3 */
+       PPY_CFG_OPERANDS_F16X2 };       /* + w_f16x2, scale_f16x2, amax_in (posbias_f16x2 beside a posbias) */
+enum { PPY_CFG_SPLITK_NONE = 0,        /* splitk == 1 only */
+       PPY_CFG_SPLITK_WORKSPACE,       /* partial sums in the workspace (ppy_conv2d_workspace_bytes) + a combine launch */
+       PPY_CFG_SPLITK_IN_WORKGROUP };  /* k-parts inside the workgroup: no workspace, no second launch */
+typedef struct ppy_conv_cfg_info {
+    int family;            /* PPY_CFG_* */
+    int local;             /* the id inside the dispatch switch of the family's source file */
+    int operands;          /* PPY_CFG_OPERANDS_* */
+    int bm, bn, stages;    /* tile rows, columns, LDS stages asked for (0 where the notion does not apply) */
+    int splitk_mode;       /* PPY_CFG_SPLITK_* */
+    int reads_presplit;    /* takes x_split_scale (ppy_conv2d_bn_act_split_f32) */
+    int writes_presplit;   /* takes y_split_scale */
+    int bn_stats;          /* its epilogue can write the BatchNorm partials of ppy_conv2d_train_fwd_f32 */
+    int stats_twin;        /* bn_stats == 0 and an otherwise identical tile has them: that tile's cfg id; else -1 */
+} ppy_conv_cfg_info;
+/* PPY_OK, or PPY_ERR_BAD_ARG for cfg outside [0, ppy_conv2d_num_configs()). */
+int ppy_conv2d_config_info(int cfg, ppy_conv_cfg_info *out);
 /* First cfg id of the streaming 1x1 kernel (csrc/conv_stream.hip; two ids) and of the patch kernel for the 3x3 stem layers
  * with C = 32, K = 32 / 64, stride 1 (csrc/conv_patch.hip; one id) -- both f16x2 only; an explicit id on a geometry the kernel
  * does not cover is PPY_ERR_BAD_ARG. */

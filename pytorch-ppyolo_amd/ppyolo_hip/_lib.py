@@ -4,7 +4,9 @@
 bound with the stdlib.  There is NO fallback: if the shared library is missing the
 import of any op raises, and every call checks the C return code.
 """
+import collections
 import ctypes
+import functools
 import os
 from ctypes import c_double, c_float, c_int, c_longlong, c_size_t, c_ulonglong, c_void_p
 
@@ -20,6 +22,13 @@ class PPYoloHipError(RuntimeError):
 
 
 _lib = None
+
+
+class ConvCfgInfo(ctypes.Structure):
+    """ppy_conv_cfg_info (include/ppyolo_hip.h)."""
+    _fields_ = [(f, c_int) for f in ('family', 'local', 'operands', 'bm', 'bn', 'stages', 'splitk_mode', 'reads_presplit',
+                                     'writes_presplit', 'bn_stats', 'stats_twin')]
+
 
 _PROTOS = {
     'ppy_version': (c_int, []),
@@ -45,6 +54,7 @@ _PROTOS = {
     'ppy_conv1x1_stats_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
     'ppy_conv1x1_bn_apply_f32': (c_int, [c_void_p, c_int] + [c_void_p] * 8 + [c_int, c_void_p, c_int] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p]),
     'ppy_conv2d_num_configs': (c_int, []),
+    'ppy_conv2d_config_info': (c_int, [c_int, ctypes.POINTER(ConvCfgInfo)]),
     'ppy_conv2d_stream_first_config': (c_int, []),
     'ppy_conv2d_patch_first_config': (c_int, []),
     'ppy_conv2d_ws_first_config': (c_int, []),
@@ -163,3 +173,29 @@ def check(rc, what=''):
         if rc == -4:                  # PPY_ERR_LAUNCH: say which HIP error it was
             msg += ' [%s]' % lib().ppy_last_hip_error().decode()
         raise PPYoloHipError('%s failed: %s (code %d)' % (what or 'libppyolo_hip call', msg, rc))
+
+
+# ppy_conv_cfg_info as Python reads it: enums by name (in the header's order; `operands` as engine.math_mode names them), flags as bools
+CFG_FAMILIES = ('fp32', 'bf16x3', 'f16x2', 'f16x2_slab', 'f16x2_tall', 'stream', 'patch', 'ws', 'ws_pre', 'kparity', 'small')
+CFG_OPERANDS = ('fp32', 'bf16x3', 'f16x2')
+CFG_SPLITK = ('none', 'workspace', 'workgroup')
+ConvCfg = collections.namedtuple('ConvCfg', 'id family local operands bm bn stages splitk_mode reads_presplit writes_presplit bn_stats stats_twin')
+
+
+@functools.lru_cache(None)
+def conv_cfgs():
+    """What every conv cfg id is and can do (ppy_conv2d_config_info): a list of ConvCfg indexed by id, read from the library once."""
+    out = []
+    for cfg in range(lib().ppy_conv2d_num_configs()):
+        d = ConvCfgInfo()
+        check(lib().ppy_conv2d_config_info(cfg, ctypes.byref(d)), 'ppy_conv2d_config_info')
+        out.append(ConvCfg(cfg, CFG_FAMILIES[d.family], d.local, CFG_OPERANDS[d.operands], d.bm, d.bn, d.stages, CFG_SPLITK[d.splitk_mode],
+                           bool(d.reads_presplit), bool(d.writes_presplit), bool(d.bn_stats), d.stats_twin))
+    return out
+
+
+def conv_cfg(cfg):
+    """The ConvCfg of one explicit id (the library's own choice, cfg < 0, has no descriptor)."""
+    if not 0 <= cfg < len(conv_cfgs()):
+        raise PPYoloHipError('no conv cfg id %d' % cfg)
+    return conv_cfgs()[cfg]

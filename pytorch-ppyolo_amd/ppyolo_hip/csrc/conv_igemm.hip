@@ -367,51 +367,47 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN)) conv_igemm_glds_ke
 #endif
 }
 
+// The configuration ids of this file, the exact-fp32 tiles.  bkt = 0: VGPR-staged loader (conv_igemm_kernel) -- [0,7) with 4 waves;
+// [7,14) with 8 waves (512 threads): two waves per SIMD inside ONE workgroup share the operand tiles -> half the L2->LDS traffic and
+// barriers per MFMA.  [14,31): LDS-DMA loader (conv_igemm_glds_kernel) with `stages` LDS stages of depth bkt (BKT).
 struct TileCfg {
-    int bm, bn, wm, wn;
+    int bm, bn, wm, wn, stages, bkt;
 };
 constexpr TileCfg kCfgs[] = {
-    {128, 128, 64, 64},  // 0
-    {128, 64, 64, 32},   // 1
-    {64, 128, 32, 64},   // 2
-    {64, 64, 32, 32},    // 3
-    {256, 32, 64, 32},   // 4
-    {128, 32, 32, 32},   // 5
-    {32, 128, 32, 32},   // 6
+    {128, 128, 64, 64, 2, 0},    // 0
+    {128, 64, 64, 32, 2, 0},     // 1
+    {64, 128, 32, 64, 2, 0},     // 2
+    {64, 64, 32, 32, 2, 0},      // 3
+    {256, 32, 64, 32, 2, 0},     // 4
+    {128, 32, 32, 32, 2, 0},     // 5
+    {32, 128, 32, 32, 2, 0},     // 6
+    {128, 128, 32, 64, 2, 0},    // 7
+    {128, 128, 64, 32, 2, 0},    // 8
+    {128, 64, 32, 32, 2, 0},     // 9
+    {64, 128, 32, 32, 2, 0},     // 10
+    {256, 64, 64, 32, 2, 0},     // 11
+    {256, 128, 64, 64, 2, 0},    // 12
+    {128, 256, 64, 64, 2, 0},    // 13
+    {64, 64, 32, 32, 3, 32},     // 14
+    {64, 64, 32, 32, 2, 32},     // 15
+    {128, 64, 32, 32, 3, 32},    // 16  (8 waves)
+    {64, 128, 32, 32, 3, 32},    // 17  (8 waves)
+    {128, 128, 32, 64, 2, 32},   // 18  (8 waves)
+    {128, 128, 64, 32, 2, 32},   // 19  (8 waves)
+    {128, 128, 64, 64, 2, 32},   // 20
+    {128, 64, 64, 32, 3, 32},    // 21
+    {64, 128, 32, 64, 3, 32},    // 22
+    {128, 32, 32, 32, 3, 32},    // 23
+    {32, 128, 32, 32, 3, 32},    // 24
+    {256, 64, 64, 32, 2, 32},    // 25  (8 waves)
+    {128, 128, 64, 64, 2, 16},   // 26  4 waves, 32 KB
+    {128, 128, 64, 64, 3, 16},   // 27  4 waves, 48 KB
+    {128, 128, 64, 32, 3, 16},   // 28  8 waves, 48 KB
+    {128, 64, 64, 32, 3, 16},    // 29  4 waves, 36 KB
+    {64, 64, 32, 32, 3, 16},     // 30  4 waves, 24 KB
 };
-constexpr int kNumTiles = sizeof(kCfgs) / sizeof(kCfgs[0]);
-// Configuration ids:
-//   [0,7)   4-wave tiles, VGPR-staged loader                      (kCfgs above)
-//   [7,14)  8-wave (512-thread) tiles, VGPR-staged loader: two waves per SIMD inside ONE
-//           workgroup share the operand tiles -> half the L2->LDS traffic and barriers per MFMA
-//           {128,128,32,64} {128,128,64,32} {128,64,32,32} {64,128,32,32} {256,64,64,32}
-//           {256,128,64,64} {128,256,64,64}
-//   [14,26) LDS-DMA loader (conv_igemm_glds_kernel), see kGlds below
-struct GldsCfg {
-    int bm, bn, wm, wn, stages;
-};
-constexpr GldsCfg kGlds[] = {
-    {64, 64, 32, 32, 3},     // 14
-    {64, 64, 32, 32, 2},     // 15
-    {128, 64, 32, 32, 3},    // 16  (8 waves)
-    {64, 128, 32, 32, 3},    // 17  (8 waves)
-    {128, 128, 32, 64, 2},   // 18  (8 waves)
-    {128, 128, 64, 32, 2},   // 19  (8 waves)
-    {128, 128, 64, 64, 2},   // 20
-    {128, 64, 64, 32, 3},    // 21
-    {64, 128, 32, 64, 3},    // 22
-    {128, 32, 32, 32, 3},    // 23
-    {32, 128, 32, 32, 3},    // 24
-    {256, 64, 64, 32, 2},    // 25  (8 waves)
-    // stage depth 16 (BKT): [26,31)
-    {128, 128, 64, 64, 2},   // 26  4 waves, 32 KB
-    {128, 128, 64, 64, 3},   // 27  4 waves, 48 KB
-    {128, 128, 64, 32, 3},   // 28  8 waves, 48 KB
-    {128, 64, 64, 32, 3},    // 29  4 waves, 36 KB
-    {64, 64, 32, 32, 3},     // 30  4 waves, 24 KB
-};
-constexpr int kNumGlds = sizeof(kGlds) / sizeof(kGlds[0]);
-constexpr int kNumCfgs = 14 + kNumGlds;
+constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+constexpr int kNumTiles = 7;      // the tiles pick_config's cost model knows
 
 template <int BM, int BN, int WM, int WN, bool SPLIT, bool VEC>
 int launch_one(const ConvArgs &p, int splits, size_t lds, int tiles, hipStream_t stream) {
@@ -519,10 +515,9 @@ void pick_config(const Geometry &g, int K, int *cfg_out, int *split_out) {
 
 }  // namespace
 
-// configuration ids [kNumCfgs, kNumCfgs + ppy_x3_num_configs()) select the split-bf16 kernels of conv_x3.hip, the ids after
-// them the streaming kernel of conv_stream.hip (1x1, C = 64 / 128, f16x2 operands: ppy_conv2d_stream_first_config() + {0, 1}),
-// then the patch kernel of conv_patch.hip (3x3 / stride 1, C = 32, K = 32 / 64, f16x2 operands), then the f16x2 tiles with
-// specialised waves of conv_ws.hip
+// The global ids, composed from the families' counts: this file's kNumCfgs, then conv_x3.hip, conv_stream.hip, conv_patch.hip,
+// conv_ws.hip, conv_small.hip.  The *_first() below serve this composition and the hand-over to a family's dispatch only: what an id
+// can do is read from its descriptor (ppy_conv2d_config_info).
 static int stream_first() { return kNumCfgs + ppy_x3_num_configs(); }
 static int patch_first() { return stream_first() + ppy_stream_num_configs(); }
 static int ws_first() { return patch_first() + ppy_patch_num_configs(); }
@@ -532,6 +527,26 @@ extern "C" int ppy_conv2d_ws_first_config(void) { return ws_first(); }
 extern "C" int ppy_conv2d_small_first_config(void) { return small_first(); }
 extern "C" int ppy_conv2d_stream_first_config(void) { return stream_first(); }
 extern "C" int ppy_conv2d_patch_first_config(void) { return patch_first(); }
+
+// this file's ids: fp32 operands and tensors only, split-K through the workspace, no BatchNorm statistics
+static int ppy_fp32_config_info(int c, ppy_conv_cfg_info *out) {
+    if (c < 0 || c >= kNumCfgs) return PPY_ERR_BAD_ARG;
+    *out = ppy_cfg_info(PPY_CFG_FP32, c, PPY_CFG_OPERANDS_FP32, kCfgs[c].bm, kCfgs[c].bn, kCfgs[c].stages, PPY_CFG_SPLITK_WORKSPACE, false, false, false);
+    return PPY_OK;
+}
+
+extern "C" int ppy_conv2d_config_info(int cfg, ppy_conv_cfg_info *out) {
+    if (!out || cfg < 0 || cfg >= ppy_conv2d_num_configs()) return PPY_ERR_BAD_ARG;
+    int base = 0, rc;
+    if (cfg >= small_first()) rc = ppy_small_config_info(cfg - (base = small_first()), out);
+    else if (cfg >= ws_first()) rc = ppy_ws_config_info(cfg - (base = ws_first()), out);
+    else if (cfg >= patch_first()) rc = ppy_patch_config_info(cfg - (base = patch_first()), out);
+    else if (cfg >= stream_first()) rc = ppy_stream_config_info(cfg - (base = stream_first()), out);
+    else if (cfg >= kNumCfgs) rc = ppy_x3_config_info(cfg - (base = kNumCfgs), out);
+    else rc = ppy_fp32_config_info(cfg, out);
+    if (rc == PPY_OK && out->stats_twin >= 0) out->stats_twin += base;
+    return rc;
+}
 
 extern "C" int ppy_conv2d_pick(int N, int H, int W, int C, int K, int R, int S, int stride, int pad,
                                int *cfg_out, int *splitk_out) {
@@ -563,7 +578,8 @@ extern "C" size_t ppy_conv2d_workspace_bytes(int N, int H, int W, int C, int K, 
     if (!conv_geometry(N, H, W, C, K, R, S, stride, pad, &g)) return 0;
     int c, s;
     if (resolve(g, K, cfg, splitk, &c, &s) != PPY_OK) return 0;
-    if (c >= small_first()) return 0;      // (conv_small.hip splits the reduction inside the workgroup)
+    ppy_conv_cfg_info d;
+    if (ppy_conv2d_config_info(c, &d) != PPY_OK || d.splitk_mode != PPY_CFG_SPLITK_WORKSPACE) return 0;
     return s > 1 ? (size_t)s * g.M * K * sizeof(float) : 0;
 }
 
@@ -573,6 +589,24 @@ static unsigned long long *g_trace = nullptr;
 // real-time counter), HW_ID and XCC_ID of every workgroup of the following launches to `buf`
 // (4 x u64 per workgroup); tools/conv_trace.py turns that into a per-CU timeline.
 extern "C" void ppy_debug_set_trace(unsigned long long *buf) { g_trace = buf; }
+
+// The kernels' argument struct for a plain launch: fp32 or f16x2 operands, no shortcut, position bias, upsampling or pre-split
+// tensor, one split, nothing tracked on the way out.  Every entry point below starts from it and sets what differs.
+static ConvArgs conv_args(const Geometry &g, const float *x, int x_ld, const float *w_krsc, const void *w_f16x2, const float *scale_f16x2,
+                          const float *scale, const float *shift, float *y, int y_ld, int N, int H, int W, int C, int K, int R, int S,
+                          int stride, int pad, int act, const float *amax_in) {
+    ConvArgs p;
+    p.x = x; p.w = w_krsc; p.w3 = nullptr; p.wf16 = (const unsigned short *)w_f16x2;
+    p.scale_f16 = scale_f16x2; p.posb_f16 = nullptr; p.amax_in = amax_in; p.amax_out = nullptr; p.scale = scale; p.shift = shift;
+    p.res = nullptr; p.posb = nullptr; p.y = y; p.part = nullptr;
+    p.x_ld = x_ld; p.res_ld = 0; p.y_ld = y_ld;
+    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = g.Ho; p.Wo = g.Wo; p.K = K; p.R = R; p.S = S;
+    p.stride = stride; p.pad = pad; p.act = act; p.ups = 0;
+    p.M = g.M; p.Kred = g.Kred; p.cchunks = C / BK; p.chunks_total = g.chunks; p.chunks_per_split = g.chunks;
+    p.nstages = 2;
+    p.trace = nullptr;
+    return p;
+}
 
 static int conv2d_impl(const float *x, int x_ld, const float *w_krsc, const void *w_x3,
                        const void *w_f16x2, const float *scale, const float *scale_f16x2,
@@ -598,27 +632,27 @@ static int conv2d_impl(const float *x, int x_ld, const float *w_krsc, const void
     if (cfg < 0 && w_x3 && K >= 48 && g.chunks >= 4) c = kNumCfgs + 4;
     if (cfg < 0 && w_f16x2 && scale_f16x2 && amax_in && (!posbias || posbias_f16x2) && K >= 48 && g.chunks >= 4)
         c = kNumCfgs + ppy_x3_f16_base() + 4;      // the same tile on the f16x2 kernel
-    if (s > 1 && c < small_first()) {
+    ppy_conv_cfg_info d;
+    if (ppy_conv2d_config_info(c, &d) != PPY_OK) return PPY_ERR_BAD_ARG;
+    if (s > 1 && d.splitk_mode == PPY_CFG_SPLITK_WORKSPACE) {
         const size_t need = (size_t)s * g.M * K * sizeof(float);
         if (!ws || ws_bytes < need) return PPY_ERR_WORKSPACE;
     }
-    ConvArgs p;
-    p.x = x; p.w = w_krsc; p.w3 = (const unsigned short *)w_x3; p.wf16 = (const unsigned short *)w_f16x2;
-    p.scale_f16 = scale_f16x2; p.posb_f16 = posbias_f16x2; p.amax_in = amax_in; p.amax_out = amax_out; p.scale = scale; p.shift = shift; p.res = residual; p.posb = posbias;
+    ConvArgs p = conv_args(g, x, x_ld, w_krsc, w_f16x2, scale_f16x2, scale, shift, y, y_ld, N, H, W, C, K, R, S, stride, pad, act, amax_in);
+    p.w3 = (const unsigned short *)w_x3;
+    p.posb_f16 = posbias_f16x2; p.amax_out = amax_out; p.res = residual; p.res_ld = res_ld; p.posb = posbias;
     p.amax_in2 = amax_in ? amax_in2 : nullptr;
-    p.y = y; p.part = (float *)ws;
-    p.x_ld = x_ld; p.res_ld = res_ld; p.y_ld = y_ld;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = g.Ho; p.Wo = g.Wo; p.K = K; p.R = R; p.S = S;
-    p.stride = stride; p.pad = pad; p.act = act; p.ups = upsample2x ? 1 : 0;
-    p.M = g.M; p.Kred = g.Kred; p.cchunks = C / BK; p.chunks_total = g.chunks;
+    p.part = (float *)ws;
+    p.ups = upsample2x ? 1 : 0;
     p.chunks_per_split = ceil_div(g.chunks, s);
-    p.nstages = 2;
     p.trace = g_trace;
     p.xscale = x_split_scale; p.yscale = y_split_scale; p.ysplit_mul = y_bound_mul; p.ysplit_add = y_bound_add;
     hipStream_t st = (hipStream_t)stream;
     rc = dispatch_cfg(p, c, s, st);
-    if (rc == PPY_ERR_UNSUPPORTED && c >= 14 && !x_split_scale && !y_split_scale) {
-        // LDS-DMA kernel declined (tensor >= 4 GB: 32-bit DMA offsets): VGPR-staged kernel, 64x64 tiles
+    if (rc == PPY_ERR_UNSUPPORTED && !x_split_scale && !y_split_scale) {
+        // the chosen kernel declined (tensor >= 4 GB: 32-bit DMA offsets; a shape without a scalar epilogue): VGPR-staged fp32 kernel,
+        // 64x64 tiles, which declines nothing.  Its split-K goes through the workspace: checked above only if the chosen id's does too
+        if (s > 1 && d.splitk_mode != PPY_CFG_SPLITK_WORKSPACE) return PPY_ERR_UNSUPPORTED;
         rc = dispatch_cfg(p, 3, s, st);
     }
     return rc;
@@ -655,7 +689,9 @@ extern "C" int ppy_conv2d_bn_act_split_f32(const float *x, int x_ld, const float
         return conv2d_impl(x, x_ld, w_krsc, w_x3, w_f16x2, scale, scale_f16x2, shift, residual, res_ld, posbias, posbias_f16x2, y, y_ld, N,
                            H, W, C, K, R, S, stride, pad, act, upsample2x, cfg, splitk, amax_in, amax_out, ws, ws_bytes, stream, nullptr,
                            nullptr, 0.f, 0.f, amax_in2);
-    PPY_CHECK_ARG(cfg >= 0 && (splitk <= 1 || cfg >= small_first()) && !(upsample2x && y_split_scale));      // (conv_small.hip: the k-parts never leave the launch)
+    ppy_conv_cfg_info d;
+    PPY_CHECK_ARG(ppy_conv2d_config_info(cfg, &d) == PPY_OK && !(upsample2x && y_split_scale));
+    PPY_CHECK_ARG(splitk <= 1 || d.splitk_mode == PPY_CFG_SPLITK_IN_WORKGROUP);      // (the k-parts must not leave the launch)
     PPY_CHECK_ARG(!y_split_scale || (y_bound_mul >= 0.f && y_bound_add >= 0.f && K % 32 == 0 && y_ld % 32 == 0 && ((uintptr_t)y & 127) == 0));
     PPY_CHECK_ARG(!x_split_scale || (C % 32 == 0 && x_ld % 32 == 0 && ((uintptr_t)x & 127) == 0));
     return conv2d_impl(x, x_ld, w_krsc, w_x3, w_f16x2, scale, scale_f16x2, shift, residual, res_ld, posbias, posbias_f16x2, y, y_ld, N, H,
@@ -663,48 +699,27 @@ extern "C" int ppy_conv2d_bn_act_split_f32(const float *x, int x_ld, const float
                        y_split_scale, y_bound_mul, y_bound_add, amax_in2);
 }
 
+#define TILE_CASE(i) case i: return launch_cfg<kCfgs[i].bm, kCfgs[i].bn, kCfgs[i].wm, kCfgs[i].wn>(p, s, st)
+#define GLDS_CASE(i) case i: return launch_glds<kCfgs[i].bm, kCfgs[i].bn, kCfgs[i].wm, kCfgs[i].wn, kCfgs[i].stages, kCfgs[i].bkt>(p, s, st)
 static int dispatch_cfg(const ConvArgs &p, int c, int s, hipStream_t st) {
-    // (statistics from the epilogue exist in the f16x2 kernels only: conv_x3.hip's tiles, conv_stream.hip, conv_patch.hip, conv_ws.hip)
-    if (p.bn_part && c < kNumCfgs + ppy_x3_f16_base()) return PPY_ERR_UNSUPPORTED;
-    // pre-split tensors exist on the f16x2 tiles (conv_x3.hip, conv_ws.hip) only: anything else would misread the bytes
-    if ((p.xscale || p.yscale) && (c < kNumCfgs + ppy_x3_f16_base() || (c >= stream_first() && c < ws_first()))) return PPY_ERR_BAD_ARG;
-    if (c >= small_first()) return ppy_small_dispatch(p, c - small_first(), s, st);
-    if (c >= ws_first()) return ppy_ws_dispatch(p, c - ws_first(), s, st);
-    if (c >= patch_first()) return s == 1 ? ppy_patch_dispatch(p, c - patch_first(), st) : PPY_ERR_BAD_ARG;
-    if (c >= stream_first()) return s == 1 ? ppy_stream_dispatch(p, c - stream_first(), nullptr, 0, st) : PPY_ERR_BAD_ARG;
-    if (c >= kNumCfgs) return ppy_x3_dispatch(p, c - kNumCfgs, s, st);
+    ppy_conv_cfg_info d;
+    if (ppy_conv2d_config_info(c, &d) != PPY_OK) return PPY_ERR_BAD_ARG;
+    if (p.bn_part && !d.bn_stats) return PPY_ERR_UNSUPPORTED;
+    // a kernel that does not know pre-split tensors would misread the bytes
+    if ((p.xscale && !d.reads_presplit) || (p.yscale && !d.writes_presplit)) return PPY_ERR_BAD_ARG;
+    if (s != 1 && d.splitk_mode == PPY_CFG_SPLITK_NONE) return PPY_ERR_BAD_ARG;
+    const int f = d.family;
+    if (f == PPY_CFG_SMALL) return ppy_small_dispatch(p, d.local, s, st);
+    if (f == PPY_CFG_WS || f == PPY_CFG_WS_PRE || f == PPY_CFG_WS_KPARITY) return ppy_ws_dispatch(p, d.local, s, st);
+    if (f == PPY_CFG_PATCH) return ppy_patch_dispatch(p, d.local, st);
+    if (f == PPY_CFG_STREAM) return ppy_stream_dispatch(p, d.local, nullptr, 0, st);
+    if (f != PPY_CFG_FP32) return ppy_x3_dispatch(p, d.local, s, st);      // bf16x3 and the three kinds of f16x2 tiles
     switch (c) {
-        case 0: return launch_cfg<128, 128, 64, 64>(p, s, st);
-        case 1: return launch_cfg<128, 64, 64, 32>(p, s, st);
-        case 2: return launch_cfg<64, 128, 32, 64>(p, s, st);
-        case 3: return launch_cfg<64, 64, 32, 32>(p, s, st);
-        case 4: return launch_cfg<256, 32, 64, 32>(p, s, st);
-        case 5: return launch_cfg<128, 32, 32, 32>(p, s, st);
-        case 6: return launch_cfg<32, 128, 32, 32>(p, s, st);
-        case 7: return launch_cfg<128, 128, 32, 64>(p, s, st);
-        case 8: return launch_cfg<128, 128, 64, 32>(p, s, st);
-        case 9: return launch_cfg<128, 64, 32, 32>(p, s, st);
-        case 10: return launch_cfg<64, 128, 32, 32>(p, s, st);
-        case 11: return launch_cfg<256, 64, 64, 32>(p, s, st);
-        case 12: return launch_cfg<256, 128, 64, 64>(p, s, st);
-        case 13: return launch_cfg<128, 256, 64, 64>(p, s, st);
-        case 14: return launch_glds<64, 64, 32, 32, 3>(p, s, st);
-        case 15: return launch_glds<64, 64, 32, 32, 2>(p, s, st);
-        case 16: return launch_glds<128, 64, 32, 32, 3>(p, s, st);
-        case 17: return launch_glds<64, 128, 32, 32, 3>(p, s, st);
-        case 18: return launch_glds<128, 128, 32, 64, 2>(p, s, st);
-        case 19: return launch_glds<128, 128, 64, 32, 2>(p, s, st);
-        case 20: return launch_glds<128, 128, 64, 64, 2>(p, s, st);
-        case 21: return launch_glds<128, 64, 64, 32, 3>(p, s, st);
-        case 22: return launch_glds<64, 128, 32, 64, 3>(p, s, st);
-        case 23: return launch_glds<128, 32, 32, 32, 3>(p, s, st);
-        case 24: return launch_glds<32, 128, 32, 32, 3>(p, s, st);
-        case 25: return launch_glds<256, 64, 64, 32, 2>(p, s, st);
-        case 26: return launch_glds<128, 128, 64, 64, 2, 16>(p, s, st);
-        case 27: return launch_glds<128, 128, 64, 64, 3, 16>(p, s, st);
-        case 28: return launch_glds<128, 128, 64, 32, 3, 16>(p, s, st);
-        case 29: return launch_glds<128, 64, 64, 32, 3, 16>(p, s, st);
-        case 30: return launch_glds<64, 64, 32, 32, 3, 16>(p, s, st);
+        TILE_CASE(0); TILE_CASE(1); TILE_CASE(2); TILE_CASE(3); TILE_CASE(4); TILE_CASE(5); TILE_CASE(6);
+        TILE_CASE(7); TILE_CASE(8); TILE_CASE(9); TILE_CASE(10); TILE_CASE(11); TILE_CASE(12); TILE_CASE(13);
+        GLDS_CASE(14); GLDS_CASE(15); GLDS_CASE(16); GLDS_CASE(17); GLDS_CASE(18); GLDS_CASE(19); GLDS_CASE(20); GLDS_CASE(21); GLDS_CASE(22);
+        GLDS_CASE(23); GLDS_CASE(24); GLDS_CASE(25); GLDS_CASE(26); GLDS_CASE(27); GLDS_CASE(28); GLDS_CASE(29); GLDS_CASE(30);
+        static_assert(kNumCfgs == 31, "one case per row of kCfgs");
     }
     return PPY_ERR_BAD_ARG;
 }
@@ -722,16 +737,8 @@ extern "C" int ppy_conv1x1_expand_f32(const float *x, int x_ld, const void *w_f1
     if (!conv_geometry(N, H, W, C, K, 1, 1, 1, 0, &g)) return PPY_ERR_BAD_ARG;
     PPY_CHECK_ARG(x_ld >= C && y_ld >= K && (!residual || res_ld >= K));
     PPY_CHECK_ARG(act == PPY_ACT_NONE || act == PPY_ACT_RELU || act == PPY_ACT_LEAKY);
-    ConvArgs p;
-    p.x = x; p.w = nullptr; p.w3 = nullptr; p.wf16 = (const unsigned short *)w_f16x2;
-    p.scale_f16 = scale_f16x2; p.posb_f16 = nullptr; p.amax_in = amax_in; p.amax_out = amax_out; p.scale = scale_f16x2; p.shift = shift;
-    p.res = residual; p.posb = nullptr; p.y = y; p.part = nullptr;
-    p.x_ld = x_ld; p.res_ld = res_ld; p.y_ld = y_ld;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = H; p.Wo = W; p.K = K; p.R = 1; p.S = 1;
-    p.stride = 1; p.pad = 0; p.act = act; p.ups = 0;
-    p.M = g.M; p.Kred = C; p.cchunks = C / BK; p.chunks_total = g.chunks; p.chunks_per_split = g.chunks;
-    p.nstages = 2;
-    p.trace = nullptr;
+    ConvArgs p = conv_args(g, x, x_ld, nullptr, w_f16x2, scale_f16x2, scale_f16x2, shift, y, y_ld, N, H, W, C, K, 1, 1, 1, 0, act, amax_in);
+    p.amax_out = amax_out; p.res = residual; p.res_ld = res_ld;
     return ppy_stream_dispatch(p, variant, pooled, pooled_ld, (hipStream_t)stream);
 }
 
@@ -748,15 +755,7 @@ static int stream_args(ConvArgs &p, const float *x, int x_ld, const void *w_f16x
     Geometry g;
     if (!conv_geometry(N, H, W, C, K, 1, 1, 1, 0, &g)) return PPY_ERR_BAD_ARG;
     if (x_ld < C) return PPY_ERR_BAD_ARG;
-    p.x = x; p.w = nullptr; p.w3 = nullptr; p.wf16 = (const unsigned short *)w_f16x2;
-    p.scale_f16 = scale_f16x2; p.posb_f16 = nullptr; p.amax_in = amax_in; p.amax_out = nullptr; p.scale = scale_f16x2; p.shift = bias;
-    p.res = nullptr; p.posb = nullptr; p.y = nullptr; p.part = nullptr;
-    p.x_ld = x_ld; p.res_ld = 0; p.y_ld = K;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = H; p.Wo = W; p.K = K; p.R = 1; p.S = 1;
-    p.stride = 1; p.pad = 0; p.act = PPY_ACT_NONE; p.ups = 0;
-    p.M = g.M; p.Kred = C; p.cchunks = C / BK; p.chunks_total = g.chunks; p.chunks_per_split = g.chunks;
-    p.nstages = 2;
-    p.trace = nullptr;
+    p = conv_args(g, x, x_ld, nullptr, w_f16x2, scale_f16x2, scale_f16x2, bias, nullptr, K, N, H, W, C, K, 1, 1, 1, 0, PPY_ACT_NONE, amax_in);
     return PPY_OK;
 }
 
@@ -803,16 +802,8 @@ extern "C" int ppy_conv3x3_maxpool_f32(const float *x, int x_ld, const void *w_f
     if (!conv_geometry(N, H, W, C, K, 3, 3, 1, 1, &g)) return PPY_ERR_BAD_ARG;
     PPY_CHECK_ARG(x_ld >= C && pooled_ld >= K);
     PPY_CHECK_ARG(act == PPY_ACT_NONE || act == PPY_ACT_RELU || act == PPY_ACT_LEAKY);
-    ConvArgs p;
-    p.x = x; p.w = nullptr; p.w3 = nullptr; p.wf16 = (const unsigned short *)w_f16x2;
-    p.scale_f16 = scale_f16x2; p.posb_f16 = nullptr; p.amax_in = amax_in; p.amax_out = amax_out; p.scale = scale_f16x2; p.shift = shift;
-    p.res = nullptr; p.posb = nullptr; p.y = pooled; p.part = nullptr;
-    p.x_ld = x_ld; p.res_ld = 0; p.y_ld = pooled_ld;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = H; p.Wo = W; p.K = K; p.R = 3; p.S = 3;
-    p.stride = 1; p.pad = 1; p.act = act; p.ups = 0;
-    p.M = g.M; p.Kred = 9 * C; p.cchunks = C / BK; p.chunks_total = g.chunks; p.chunks_per_split = g.chunks;
-    p.nstages = 2;
-    p.trace = nullptr;
+    ConvArgs p = conv_args(g, x, x_ld, nullptr, w_f16x2, scale_f16x2, scale_f16x2, shift, pooled, pooled_ld, N, H, W, C, K, 3, 3, 1, 1, act, amax_in);
+    p.amax_out = amax_out;
     return ppy_patch_maxpool_dispatch(p, (H - 1) / 2 + 1, (W - 1) / 2 + 1, (hipStream_t)stream);
 }
 
@@ -839,16 +830,7 @@ extern "C" int ppy_conv2d_train_fwd_f32(const float *x, int x_ld, const float *w
     PPY_CHECK_ARG(x_ld >= C && x_ld % 4 == 0 && y_ld >= K && ((uintptr_t)x & 15) == 0);
     PPY_CHECK_ARG(cfg < ppy_conv2d_num_configs());
     if (bn_partials_bytes < ppy_conv2d_bn_partials_bytes(g.M, K)) return PPY_ERR_WORKSPACE;
-    ConvArgs p;
-    p.x = x; p.w = w_krsc; p.w3 = nullptr; p.wf16 = (const unsigned short *)w_f16x2;
-    p.scale_f16 = scale_f16x2; p.posb_f16 = nullptr; p.amax_in = amax_in; p.amax_out = nullptr; p.scale = scale_f16x2; p.shift = bias;
-    p.res = nullptr; p.posb = nullptr; p.y = y; p.part = nullptr;
-    p.x_ld = x_ld; p.res_ld = 0; p.y_ld = y_ld;
-    p.N = N; p.H = H; p.W = W; p.C = C; p.Ho = g.Ho; p.Wo = g.Wo; p.K = K; p.R = R; p.S = S;
-    p.stride = stride; p.pad = pad; p.act = PPY_ACT_NONE; p.ups = 0;
-    p.M = g.M; p.Kred = g.Kred; p.cchunks = C / BK; p.chunks_total = g.chunks; p.chunks_per_split = g.chunks;
-    p.nstages = 2;
-    p.trace = nullptr;
+    ConvArgs p = conv_args(g, x, x_ld, w_krsc, w_f16x2, scale_f16x2, scale_f16x2, bias, y, y_ld, N, H, W, C, K, R, S, stride, pad, PPY_ACT_NONE, amax_in);
     p.bn_part = bn_partials;
     p.bn_slices_host = bn_slices;
     p.bn_capacity = (int)bn_slice_capacity(g.M);

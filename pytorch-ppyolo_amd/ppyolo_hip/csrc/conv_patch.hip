@@ -365,6 +365,13 @@ int launch_patch(const PatchArgs &q, hipStream_t stream) {
 
 int ppy_patch_num_configs() { return 1; }
 
+// fp32 tensors only, one pass over the reduction, BatchNorm statistics from the epilogue
+int ppy_patch_config_info(int local, ppy_conv_cfg_info *out) {
+    if (local != 0) return PPY_ERR_BAD_ARG;
+    *out = ppy_cfg_info(PPY_CFG_PATCH, local, PPY_CFG_OPERANDS_F16X2, 0, 0, 0, PPY_CFG_SPLITK_NONE, false, false, true);
+    return PPY_OK;
+}
+
 int ppy_patch_dispatch(const ConvArgs &p, int local, hipStream_t stream) {
     if (local != 0) return PPY_ERR_BAD_ARG;
     // BAD_ARG, not UNSUPPORTED: an explicit id that does not apply is the caller's error (no silent other kernel)

@@ -76,9 +76,18 @@ struct Geometry {
     int Ho, Wo, M, Kred, chunks;
 };
 
+// One descriptor per tile configuration id (ppy_conv2d_config_info, include/ppyolo_hip.h).  Every family file describes its own
+// local ids in ppy_<family>_config_info, beside the switch that dispatches them; `local` and `stats_twin` are in the family's own
+// numbering there, conv_igemm.hip -- which composes the global ids -- shifts stats_twin.  PPY_ERR_BAD_ARG outside the family's ids.
+static inline ppy_conv_cfg_info ppy_cfg_info(int family, int local, int operands, int bm, int bn, int stages, int splitk_mode,
+                                             bool reads_presplit, bool writes_presplit, bool bn_stats, int stats_twin = -1) {
+    return ppy_conv_cfg_info{family, local, operands, bm, bn, stages, splitk_mode, reads_presplit, writes_presplit, bn_stats, stats_twin};
+}
+
 // conv_x3.hip: configurations of the split-bf16 kernel (ids local to that file)
 int ppy_x3_num_configs();
 int ppy_x3_f16_base();        // first local id of the f16x2 scheme
+int ppy_x3_config_info(int local_cfg, ppy_conv_cfg_info *out);
 int ppy_x3_dispatch(const ConvArgs &p, int local_cfg, int splits, hipStream_t stream);
 // conv_stream.hip: persistent streaming kernel for 1x1 convolutions with C = 64 (f16x2 operands), optional 2x2 average output
 // Tile order (round 5).  Workgroups are dealt round-robin to the 8 XCDs, each with its own L2; every XCD takes one CONTIGUOUS range of
@@ -123,17 +132,21 @@ __device__ __forceinline__ void ppy_tile_of(const ConvArgs &p, int tiles_n, int 
 #endif
 
 int ppy_stream_num_configs();
+int ppy_stream_config_info(int local_cfg, ppy_conv_cfg_info *out);
 int ppy_stream_dispatch(const ConvArgs &p, int local_cfg, float *pool, int pool_ld, hipStream_t stream);
 // conv_patch.hip: 3x3 / stride 1 / pad 1 with C = 32 (the stem layers), input patch staged once per output tile (f16x2 operands)
 int ppy_patch_num_configs();
+int ppy_patch_config_info(int local_cfg, ppy_conv_cfg_info *out);
 int ppy_patch_dispatch(const ConvArgs &p, int local_cfg, hipStream_t stream);
 int ppy_patch_maxpool_dispatch(const ConvArgs &p, int Hp, int Wp, hipStream_t stream);      // + MaxPool2d(3, 2, 1) from the epilogue; p.y = the pooled tensor
 // conv_ws.hip: the f16x2 tiles with specialised waves (four deliver operands, four multiply)
 int ppy_ws_num_configs();
+int ppy_ws_config_info(int local_cfg, ppy_conv_cfg_info *out);
 int ppy_ws_dispatch(const ConvArgs &p, int local_cfg, int splits, hipStream_t stream);
 // conv_small.hip (round 6): wave-private 32 x 32 / 32 x 64 output tiles for small outputs (batch 1, narrow layers); `splits` = k-parts
 // INSIDE the workgroup (a power of two <= its waves, anything else is rounded down): no workspace, no combine launch
 int ppy_small_num_configs();
+int ppy_small_config_info(int local_cfg, ppy_conv_cfg_info *out);
 int ppy_small_dispatch(const ConvArgs &p, int local_cfg, int splits, hipStream_t stream);
 
 namespace {

@@ -266,8 +266,20 @@ int launch_small(ConvArgs p, int nwave, int splits, hipStream_t stream) {
 
 }  // namespace
 
-// local ids: 0 = 32x32 wave tiles, four waves per workgroup; 1 = 32x64, four; 2 = 32x32, eight; 3 = 32x64, eight
-int ppy_small_num_configs() { return 4; }
+// the local ids: 32 x 32*tn output tile per wave, `nwave` waves per workgroup
+struct SmallCfg {
+    int tn, nwave;
+};
+constexpr SmallCfg kSmall[] = {{1, 4}, {2, 4}, {1, 8}, {2, 8}};
+#define SMALL_CASE(i) case i: return launch_small<kSmall[i].tn>(q, kSmall[i].nwave, s, st)
+int ppy_small_num_configs() { return sizeof(kSmall) / sizeof(kSmall[0]); }
+
+// every id: pre-split tensors on both sides, k-parts inside the workgroup, no BatchNorm statistics (launch_small)
+int ppy_small_config_info(int c, ppy_conv_cfg_info *out) {
+    if (c < 0 || c >= ppy_small_num_configs()) return PPY_ERR_BAD_ARG;
+    *out = ppy_cfg_info(PPY_CFG_SMALL, c, PPY_CFG_OPERANDS_F16X2, 32, 32 * kSmall[c].tn, 0, PPY_CFG_SPLITK_IN_WORKGROUP, true, true, false);
+    return PPY_OK;
+}
 
 int ppy_small_dispatch(const ConvArgs &p, int c, int s, hipStream_t st) {
     if (!p.wf16 || ((uintptr_t)p.wf16 & 15) != 0 || !p.scale_f16 || !p.amax_in || (p.posb && !p.posb_f16)) return PPY_ERR_BAD_ARG;
@@ -276,10 +288,11 @@ int ppy_small_dispatch(const ConvArgs &p, int c, int s, hipStream_t st) {
     q.posb = p.posb ? p.posb_f16 : nullptr;
     q.part = nullptr;
     switch (c) {
-        case 0: return launch_small<1>(q, 4, s, st);
-        case 1: return launch_small<2>(q, 4, s, st);
-        case 2: return launch_small<1>(q, 8, s, st);
-        case 3: return launch_small<2>(q, 8, s, st);
+        SMALL_CASE(0);
+        SMALL_CASE(1);
+        SMALL_CASE(2);
+        SMALL_CASE(3);
+        static_assert(sizeof(kSmall) / sizeof(kSmall[0]) == 4, "one case per descriptor");
     }
     return PPY_ERR_BAD_ARG;
 }

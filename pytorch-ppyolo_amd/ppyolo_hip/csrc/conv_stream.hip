@@ -377,6 +377,13 @@ int launch_stream(const StreamArgs &q, int grid, hipStream_t stream) {
 
 int ppy_stream_num_configs() { return 2; }
 
+// both ids: fp32 tensors only, one pass over the reduction, BatchNorm statistics from the epilogue (no tile in the GEMM sense)
+int ppy_stream_config_info(int local, ppy_conv_cfg_info *out) {
+    if (local < 0 || local >= ppy_stream_num_configs()) return PPY_ERR_BAD_ARG;
+    *out = ppy_cfg_info(PPY_CFG_STREAM, local, PPY_CFG_OPERANDS_F16X2, 0, 0, 0, PPY_CFG_SPLITK_NONE, false, false, true);
+    return PPY_OK;
+}
+
 // C = 64 (K % 64 == 0): local 0 = 512 workgroups of four waves (two per CU), local 1 = 256.  C = 128 (K % 128 == 0, K / 128 a
 // power of two): the same grids.  `pool` / `pool_ld`: optional 2x2 average of y.
 int ppy_stream_dispatch(const ConvArgs &p, int local, float *pool, int pool_ld, hipStream_t stream) {

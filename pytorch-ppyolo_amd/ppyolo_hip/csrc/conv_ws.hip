@@ -523,13 +523,43 @@ int launch_ws(ConvArgs p, int splits, hipStream_t stream) {
 
 }  // namespace
 
-// local ids: 0 = 128x128 tile with 3 stages, 1 = the same with 4, 2 = 64x128 with 4, 3 = 64x128 with 6; with the activations
-// split by the producer waves (PRE): 4 = 128x128 with 3 stages, 5 = 64x128 with 4, 6 = 128x64 with 4; eight consumer waves (4 x 2)
-// + four producers on a 256x128 tile: 7 = two stages, 8 = three; round 6, eight consumer waves as two k-parity groups (KP) on a
-// 128x128 tile: 9 = three stages, 10 = four; on a 64x128 tile (32x64 wave tiles): 11 = four stages, 12 = six; with TWO chunks per stage
-// (one barrier per 64-deep step): 13 = 128x128 with two stages, 14 / 15 = 64x128 with two / three
-// (256x128 / 128x256 with 2 x 2 consumer waves: 128 accumulator + 128 shortcut-prefetch registers spill)
-int ppy_ws_num_configs() { return 16; }
+// The local ids.  PRE: the activations are split by the producer waves (no pre-split input: launch_ws).  256x128: eight consumer
+// waves (4 x 2) + four producers.  KP (round 6): eight consumer waves as two k-parity groups; no BatchNorm statistics (launch_ws), so
+// the training forward runs `twin`, the same tile and LDS depth with one consumer group.  cps = 2: two 32-deep chunks per stage, one
+// barrier per 64-deep step.  (256x128 / 128x256 with 2 x 2 consumer waves: 128 accumulator + 128 shortcut-prefetch registers spill)
+struct WsCfg {
+    int bm, bn, ns;
+    bool pre, kp;
+    int cps, twin;
+};
+constexpr WsCfg kWs[] = {
+    {128, 128, 3, false, false, 1, -1},   // 0
+    {128, 128, 4, false, false, 1, -1},   // 1
+    {64, 128, 4, false, false, 1, -1},    // 2
+    {64, 128, 6, false, false, 1, -1},    // 3
+    {128, 128, 3, true, false, 1, -1},    // 4
+    {64, 128, 4, true, false, 1, -1},     // 5
+    {128, 64, 4, true, false, 1, -1},     // 6
+    {256, 128, 2, false, false, 1, -1},   // 7
+    {256, 128, 3, false, false, 1, -1},   // 8
+    {128, 128, 3, false, true, 1, 0},     // 9
+    {128, 128, 4, false, true, 1, 1},     // 10
+    {64, 128, 4, false, true, 1, 2},      // 11
+    {64, 128, 6, false, true, 1, 3},      // 12
+    {128, 128, 2, false, true, 2, 1},     // 13
+    {64, 128, 2, false, true, 2, 2},      // 14
+    {64, 128, 3, false, true, 2, 3},      // 15
+};
+#define WS_CASE(i) case i: return launch_ws<kWs[i].bm, kWs[i].bn, kWs[i].ns, kWs[i].pre, kWs[i].kp, kWs[i].cps>(q, s, st)
+int ppy_ws_num_configs() { return sizeof(kWs) / sizeof(kWs[0]); }
+
+int ppy_ws_config_info(int c, ppy_conv_cfg_info *out) {
+    if (c < 0 || c >= ppy_ws_num_configs()) return PPY_ERR_BAD_ARG;
+    const WsCfg &t = kWs[c];
+    *out = ppy_cfg_info(t.pre ? PPY_CFG_WS_PRE : (t.kp ? PPY_CFG_WS_KPARITY : PPY_CFG_WS), c, PPY_CFG_OPERANDS_F16X2, t.bm, t.bn, t.ns,
+                        PPY_CFG_SPLITK_WORKSPACE, !t.pre, true, !t.kp, t.twin);
+    return PPY_OK;
+}
 
 int ppy_ws_dispatch(const ConvArgs &p, int c, int s, hipStream_t st) {
     if (!p.wf16 || ((uintptr_t)p.wf16 & 15) != 0 || !p.scale_f16 || !p.amax_in || (p.posb && !p.posb_f16)) return PPY_ERR_BAD_ARG;
@@ -537,22 +567,23 @@ int ppy_ws_dispatch(const ConvArgs &p, int c, int s, hipStream_t st) {
     q.scale = p.scale_f16;
     q.posb = p.posb ? p.posb_f16 : nullptr;
     switch (c) {
-        case 0: return launch_ws<128, 128, 3>(q, s, st);
-        case 1: return launch_ws<128, 128, 4>(q, s, st);
-        case 2: return launch_ws<64, 128, 4>(q, s, st);
-        case 3: return launch_ws<64, 128, 6>(q, s, st);
-        case 4: return launch_ws<128, 128, 3, true>(q, s, st);
-        case 5: return launch_ws<64, 128, 4, true>(q, s, st);
-        case 6: return launch_ws<128, 64, 4, true>(q, s, st);
-        case 7: return launch_ws<256, 128, 2>(q, s, st);
-        case 8: return launch_ws<256, 128, 3>(q, s, st);
-        case 9: return launch_ws<128, 128, 3, false, true>(q, s, st);
-        case 10: return launch_ws<128, 128, 4, false, true>(q, s, st);
-        case 11: return launch_ws<64, 128, 4, false, true>(q, s, st);
-        case 12: return launch_ws<64, 128, 6, false, true>(q, s, st);
-        case 13: return launch_ws<128, 128, 2, false, true, 2>(q, s, st);
-        case 14: return launch_ws<64, 128, 2, false, true, 2>(q, s, st);
-        case 15: return launch_ws<64, 128, 3, false, true, 2>(q, s, st);
+        WS_CASE(0);
+        WS_CASE(1);
+        WS_CASE(2);
+        WS_CASE(3);
+        WS_CASE(4);
+        WS_CASE(5);
+        WS_CASE(6);
+        WS_CASE(7);
+        WS_CASE(8);
+        WS_CASE(9);
+        WS_CASE(10);
+        WS_CASE(11);
+        WS_CASE(12);
+        WS_CASE(13);
+        WS_CASE(14);
+        WS_CASE(15);
+        static_assert(sizeof(kWs) / sizeof(kWs[0]) == 16, "one case per descriptor");
     }
     return PPY_ERR_BAD_ARG;
 }

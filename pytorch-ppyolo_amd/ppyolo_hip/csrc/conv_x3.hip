@@ -737,47 +737,40 @@ int launch_x3(ConvArgs p, int splits, hipStream_t stream, int nstages = 2) {
     return ppy_launch_status();
 }
 
+#define X3_CASE(T, i, ...) case i: return launch_x3<T[i].bm, T[i].bn, T[i].wm, T[i].wn, __VA_ARGS__>(p, s, st, ns)
+#define X3_CASES(...)                                                                                               \
+    X3_CASE(kX3, 0, __VA_ARGS__); X3_CASE(kX3, 1, __VA_ARGS__); X3_CASE(kX3, 2, __VA_ARGS__); X3_CASE(kX3, 3, __VA_ARGS__); \
+    X3_CASE(kX3, 4, __VA_ARGS__); X3_CASE(kX3, 5, __VA_ARGS__); X3_CASE(kX3, 6, __VA_ARGS__); X3_CASE(kX3, 7, __VA_ARGS__); \
+    X3_CASE(kX3, 8, __VA_ARGS__);                                                                                   \
+    static_assert(kNumX3 == 9, "one case per tile")
+
 int dispatch_slab(const ConvArgs &p, int c, int s, hipStream_t st, int ns) {
-    switch (c) {
-        case 0: return launch_x3<256, 128, 64, 128, true, true>(p, s, st, ns);
-        case 1: return launch_x3<128, 128, 64, 64, true, true>(p, s, st, ns);
-        case 2: return launch_x3<128, 128, 32, 128, true, true>(p, s, st, ns);
-        case 3: return launch_x3<256, 64, 64, 64, true, true>(p, s, st, ns);
-        case 4: return launch_x3<128, 64, 32, 64, true, true>(p, s, st, ns);
-        case 5: return launch_x3<256, 128, 64, 64, true, true>(p, s, st, ns);
-        case 6: return launch_x3<128, 256, 64, 128, true, true>(p, s, st, ns);
-        case 7: return launch_x3<64, 128, 32, 64, true, true>(p, s, st, ns);
-        case 8: return launch_x3<64, 64, 32, 32, true, true>(p, s, st, ns);
-    }
+    switch (c) { X3_CASES(true, true); }
     return PPY_ERR_BAD_ARG;
 }
 
 // f16x2 tiles with 96 / 192 rows (three 32-row MFMA tiles per wave): the grids of the layers are small against 256 CUs, and a
 // tile height of 1.5x fills the last round of workgroups where 128 / 256 rows leave 30-40 % of the slots empty
 // (e.g. M = 46208: 361 x 2 tiles of 128x128 on 512 slots = 1.41 rounds; 241 x 2 tiles of 192x128 = 0.94).
+constexpr X3Cfg kExtra[] = {
+    {192, 128, 96, 64},     // 4 waves (2x2), 40 KB per stage
+    {192, 256, 96, 64},     // 8 waves (2x4), 56 KB per stage
+    {96, 256, 96, 64},      // 4 waves (1x4), 44 KB per stage
+};
+constexpr int kNumExtra = sizeof(kExtra) / sizeof(kExtra[0]);
 int dispatch_extra(const ConvArgs &p, int c, int s, hipStream_t st, int ns) {
     switch (c) {
-        case 0: return launch_x3<192, 128, 96, 64, true>(p, s, st, ns);     // 4 waves (2x2), 40 KB per stage
-        case 1: return launch_x3<192, 256, 96, 64, true>(p, s, st, ns);     // 8 waves (2x4), 56 KB per stage
-        case 2: return launch_x3<96, 256, 96, 64, true>(p, s, st, ns);      // 4 waves (1x4), 44 KB per stage
+        X3_CASE(kExtra, 0, true);
+        X3_CASE(kExtra, 1, true);
+        X3_CASE(kExtra, 2, true);
+        static_assert(kNumExtra == 3, "one case per tile");
     }
     return PPY_ERR_BAD_ARG;
 }
-constexpr int kNumExtra = 3;
 
 template <bool F16>
 int dispatch_scheme(const ConvArgs &p, int c, int s, hipStream_t st, int ns = 2) {
-    switch (c) {
-        case 0: return launch_x3<256, 128, 64, 128, F16>(p, s, st, ns);
-        case 1: return launch_x3<128, 128, 64, 64, F16>(p, s, st, ns);
-        case 2: return launch_x3<128, 128, 32, 128, F16>(p, s, st, ns);
-        case 3: return launch_x3<256, 64, 64, 64, F16>(p, s, st, ns);
-        case 4: return launch_x3<128, 64, 32, 64, F16>(p, s, st, ns);
-        case 5: return launch_x3<256, 128, 64, 64, F16>(p, s, st, ns);
-        case 6: return launch_x3<128, 256, 64, 128, F16>(p, s, st, ns);
-        case 7: return launch_x3<64, 128, 32, 64, F16>(p, s, st, ns);
-        case 8: return launch_x3<64, 64, 32, 32, F16>(p, s, st, ns);
-    }
+    switch (c) { X3_CASES(F16); }
     return PPY_ERR_BAD_ARG;
 }
 
@@ -815,11 +808,29 @@ __global__ void __launch_bounds__(256) split_weights_f16_kernel(const float *w, 
 
 }  // namespace
 
-// local ids: [0, 9) bf16x3, [9, 18) f16x2 (two LDS stages), [18, 27) f16x2 with three stages, [27, 36) with four,
-// [36, 45) f16x2 with slab reuse (3x3 / stride 1 / pad 1 layers) and two stages, [45, 54) the same with three,
-// [54, 57) the 96 / 192-row f16x2 tiles with two stages, [57, 60) with three, [60, 63) with four
 int ppy_x3_num_configs() { return 6 * kNumX3 + 3 * kNumExtra; }
 int ppy_x3_f16_base() { return kNumX3; }
+
+// The local ids, in the blocks ppy_x3_dispatch takes apart: the kX3 tiles as bf16x3; as f16x2 with 2, 3, 4 LDS stages; as f16x2 with
+// slab reuse (3x3 / stride 1 / pad 1 layers) and 2, 3 stages; the kExtra tiles as f16x2 with 2, 3, 4 stages.  Pre-split tensors: the
+// f16x2 tiles without slab reuse; BatchNorm statistics: every f16x2 tile (launch_x3).
+int ppy_x3_config_info(int c, ppy_conv_cfg_info *out) {
+    if (c < 0 || c >= ppy_x3_num_configs()) return PPY_ERR_BAD_ARG;
+    const int local = c - kNumX3, ws = PPY_CFG_SPLITK_WORKSPACE, f16 = PPY_CFG_OPERANDS_F16X2;
+    if (c < kNumX3) {
+        *out = ppy_cfg_info(PPY_CFG_BF16X3, c, PPY_CFG_OPERANDS_BF16X3, kX3[c].bm, kX3[c].bn, 2, ws, false, false, false);
+    } else if (local >= 5 * kNumX3) {
+        const X3Cfg &t = kExtra[(local - 5 * kNumX3) % kNumExtra];
+        *out = ppy_cfg_info(PPY_CFG_F16X2_TALL, c, f16, t.bm, t.bn, 2 + (local - 5 * kNumX3) / kNumExtra, ws, true, true, true);
+    } else {
+        const X3Cfg &t = kX3[local % kNumX3];
+        if (local >= 3 * kNumX3)
+            *out = ppy_cfg_info(PPY_CFG_F16X2_SLAB, c, f16, t.bm, t.bn, 2 + (local / kNumX3 - 3), ws, false, false, true);
+        else
+            *out = ppy_cfg_info(PPY_CFG_F16X2, c, f16, t.bm, t.bn, 2 + local / kNumX3, ws, true, true, true);
+    }
+    return PPY_OK;
+}
 
 int ppy_x3_dispatch(const ConvArgs &p, int c, int s, hipStream_t st) {
     if (c < kNumX3) {

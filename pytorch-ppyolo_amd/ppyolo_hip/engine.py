@@ -45,8 +45,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _TUNED_PATHS = {'fp32': os.path.join(_HERE, 'tuned_gfx950.json'), 'bf16x3': os.path.join(_HERE, 'tuned_gfx950_bf16x3.json'),
                 'f16x2': os.path.join(_HERE, 'tuned_gfx950_f16x2.json')}
 _tuned = {}
-NUM_FP32_CFGS = 31       # tile configuration ids below this are the exact-fp32 MFMA kernels (conv_igemm.hip)
-NUM_X3_CFGS = 9          # then the bf16x3 kernels [31, 40), then the f16x2 kernels [40, 67): 9 tiles x {2, 3, 4} LDS stages
 
 
 def math_mode():
@@ -594,22 +592,16 @@ class HipExecutor(object):
         pinned = {a.buf for a in list(self.plan.head_outs) + list(self.plan.feats)}
         link_maxpools(self.plan.ops, self._op_io, pinned, lambda c: c.get('wf16') is not None and c.get('amax_in_id') is not None)
 
-    def _split_capable(self, cfg, consumer):
-        """Tile configurations that read (consumer) / write pre-split tensors: the f16x2 tiles of csrc/conv_x3.hip without slab
-        reuse and the specialised-wave tiles of csrc/conv_ws.hip (as consumers: those whose producer waves do not split)."""
-        f0 = NUM_FP32_CFGS + NUM_X3_CFGS
-        if f0 <= cfg < f0 + 27 or f0 + 45 <= cfg < f0 + 54:          # 9 tiles x {2, 3, 4} stages; the 96 / 192-row tiles
-            return True
-        if cfg >= K.small_first_cfg():          # the wave-private tiles for small outputs (csrc/conv_small.hip, round 6): both sides
-            return True
-        w0 = K.ws_first_cfg()
-        return cfg - w0 in ((0, 1, 2, 3, 7, 8, 9, 10, 11, 12, 13, 14, 15) if consumer else tuple(range(16)))      # (9-15: the k-parity tiles, round 6)
+    @staticmethod
+    def split_capable(cfg, consumer):
+        """Does this tile configuration read (consumer) / write pre-split tensors?"""
+        return cfg >= 0 and (K.conv_cfg(cfg).reads_presplit if consumer else K.conv_cfg(cfg).writes_presplit)
 
     @staticmethod
     def _split_leaves_launch(op):
         """Does this op's split-K go through partial sums in memory (a second launch combines them)?  Such a launch neither reads nor
-        writes pre-split tensors.  The small-output tiles (csrc/conv_small.hip) add their k-parts inside the workgroup."""
-        return op.get('splitk', 0) > 1 and not (op['op'] == 'conv' and op.get('cfg', -1) >= K.small_first_cfg())
+        writes pre-split tensors."""
+        return op.get('splitk', 0) > 1 and not (op['op'] == 'conv' and op.get('cfg', -1) >= 0 and K.conv_cfg(op['cfg']).splitk_mode == 'workgroup')
 
     def _split_pairs(self):
         """[(producer, [consumers])] that qualify STRUCTURALLY for a pre-split tensor between them (split_pairs below)."""
@@ -646,8 +638,8 @@ class HipExecutor(object):
         for pr, cons in self._split_pairs():
             if pr.get('b2b') is not None or pr.get('b2b_of') is not None:
                 continue          # (the fused pair's output is plain fp32: it is a shortcut as well)
-            if self._split_leaves_launch(pr) or not self._split_capable(pr['cfg'], False) \
-                    or any(c.get('b2b') is None and (self._split_leaves_launch(c) or not self._split_capable(c['cfg'], True)) for c in cons):
+            if self._split_leaves_launch(pr) or not self.split_capable(pr['cfg'], False) \
+                    or any(c.get('b2b') is None and (self._split_leaves_launch(c) or not self.split_capable(c['cfg'], True)) for c in cons):
                 continue          # (every reader must take the tensor in that form, or none does)
             w, sc, sh = pr['w'], pr['scale'], pr['shift']
             l1 = w.abs().double().sum(dim=(1, 2, 3))
@@ -802,18 +794,13 @@ class HipExecutor(object):
         self._side_tail = max([i for i, op in enumerate(ops) if op.get('stream', 0)], default=None) \
             if self.multi_stream else None
 
-    @staticmethod
-    def _stream_first():
-        """First tile-configuration id of the streaming 1x1 kernel."""
-        return K.stream_first_cfg()
-
     def _run_op(self, op, ws=None):
         t = op['op']
         ws = self.ws if ws is None else ws
         if t == 'conv' and op.get('b2b_of') is not None:
             return                  # (computed by the launch of the convolution in front of it)
-        if op.get('amax_in2_id') is not None and (t != 'conv' or op.get('b2b') is not None or op.get('mpool') is not None or (
-                op.get('pool') is not None and self._stream_first() <= op['cfg'] < self._stream_first() + 2)):
+        expand = t == 'conv' and op.get('pool') is not None and op['cfg'] >= 0 and K.conv_cfg(op['cfg']).family == 'stream'
+        if op.get('amax_in2_id') is not None and (t != 'conv' or op.get('b2b') is not None or op.get('mpool') is not None or expand):
             raise PPYoloHipError('plan op %s reads a buffer with two tracked-maximum blocks through an entry point that takes one' % tune_key(op))
         if t == 'conv' and op.get('b2b') is not None:
             b = op['b2b']
@@ -821,10 +808,10 @@ class HipExecutor(object):
                               self.view(b['res']), self.view(b['y']), op['t_bound'][0], op['t_bound'][1], self._amax(b.get('amax_out_id')),
                               None if b.get('pool') is None else self.view(b['pool']))
             return
-        if t == 'conv' and op.get('pool') is not None and self._stream_first() <= op['cfg'] < self._stream_first() + 2:
+        if expand:          # (the streaming kernel's own entry point writes the pooled second output)
             K.conv1x1_expand(self.view(op['x']), op['wf16'], op['shift'], self.view(op['y']), op['act'],
                              None if op['res'] is None else self.view(op['res']), self.view(op['pool']),
-                             op['cfg'] - self._stream_first(), self._amax(op.get('amax_in_id')), self._amax(op.get('amax_out_id')))
+                             K.conv_cfg(op['cfg']).local, self._amax(op.get('amax_in_id')), self._amax(op.get('amax_out_id')))
         elif t == 'conv' and op.get('mpool') is not None:
             K.conv3x3_maxpool(self.view(op['x']), op['wf16'], op['shift'], self.view(op['mpool']), op['act'],
                               self._amax(op.get('amax_in_id')), self._amax(op.get('amax_out_id')))
@@ -935,8 +922,7 @@ class HipExecutor(object):
         """Per-layer (tile config, split-K) search measured on the device: 'measure, don't
         guess'.  Results are written into the plan ops; the graph is re-captured lazily.  only_cfgs (convolutions): measure just these
         tile ids (new candidate kernels) against the layer's current entry instead of the whole table of configurations."""
-        from ._lib import lib
-        ncfg_conv = {'fp32': NUM_FP32_CFGS, 'bf16x3': NUM_FP32_CFGS + NUM_X3_CFGS}.get(self.math, lib().ppy_conv2d_num_configs())
+        cfgs_conv = [d.id for d in K.conv_cfgs() if K.CFG_OPERANDS.index(d.operands) <= K.CFG_OPERANDS.index(self.math)]      # (the operands this mode prepares)
         cfgs_dcn = K.dcnv2_configs(self.math)      # schemes up to this mode's (+ the eight-wave f16x2 tiles)
         splits = (1, 2, 3, 4, 6, 8, 9, 12, 16)
         report = []
@@ -946,7 +932,7 @@ class HipExecutor(object):
             big = 0
             for op in self.plan.ops:
                 if op['op'] in ('conv', 'dcn'):
-                    for c in (cfgs_dcn if op['op'] == 'dcn' else range(ncfg_conv)):
+                    for c in (cfgs_dcn if op['op'] == 'dcn' else cfgs_conv):
                         for s in splits:
                             o = dict(op, cfg=c, splitk=s)
                             big = max(big, self._ws_need(o))
@@ -967,7 +953,7 @@ class HipExecutor(object):
                     # a layer whose input will arrive pre-split is measured in that form on the tiles that can read it (the
                     # bytes it reads are whatever the buffer holds: the timing does not depend on the values)
                     op.pop('x_split', None)
-                    if gp_scales is not None and (s <= 1 or c >= K.small_first_cfg()) and self._split_capable(c, True):
+                    if gp_scales is not None and not self._split_leaves_launch(op) and self.split_capable(c, True):
                         op['x_split'] = gp_scales
                     try:
                         self._run_op(op)
@@ -1000,7 +986,7 @@ class HipExecutor(object):
                     return ms
 
                 cands = []
-                pool = cfgs_dcn if op['op'] == 'dcn' else (range(ncfg_conv) if only_cfgs is None else sorted(set(only_cfgs)))
+                pool = cfgs_dcn if op['op'] == 'dcn' else (cfgs_conv if only_cfgs is None else sorted(set(only_cfgs)))
                 if only_cfgs is not None and op['op'] == 'conv' and base_cfg >= 0:
                     ms = measure(base_cfg, base_split, iters)             # the current entry defends its place
                     if ms is not None:

@@ -13,7 +13,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import ACT, check, lib
+from ._lib import ACT, CFG_FAMILIES, CFG_OPERANDS, CFG_SPLITK, ConvCfg, check, conv_cfg, conv_cfgs, lib      # noqa: F401 (the descriptors: host queries)
 
 
 class View(object):
@@ -171,18 +171,10 @@ def ws_first_cfg():
     return lib().ppy_conv2d_ws_first_config()
 
 
-def ws_num_cfgs():
-    return lib().ppy_conv2d_small_first_config() - lib().ppy_conv2d_ws_first_config()
-
-
 def small_first_cfg():
     """First conv cfg id of the wave-private tiles for small outputs (csrc/conv_small.hip, round 6; four ids).  For these ids `splitk`
     counts k-parts inside the workgroup: no workspace, no combine launch, pre-split tensors allowed with splitk > 1."""
     return lib().ppy_conv2d_small_first_config()
-
-
-def small_num_cfgs():
-    return lib().ppy_conv2d_num_configs() - lib().ppy_conv2d_small_first_config()
 
 
 def patch_first_cfg():

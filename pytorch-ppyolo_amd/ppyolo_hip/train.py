@@ -24,12 +24,10 @@ import warnings
 import torch
 
 from . import ops as K
-from ._lib import PPYoloHipError
+from ._lib import PPYoloHipError, conv_cfg, conv_cfgs
 
-NUM_FP32_CFGS = 31      # ids below: exact-fp32 MFMA tiles; the next nine: bf16x3 (csrc/conv_igemm.hip, conv_x3.hip)
 TRAIN_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_gfx950_train.json')
 TRAIN_TABLE_F16 = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_gfx950_train_f16x2.json')
-NUM_X3_F16_FIRST, NUM_X3_F16_LAST = 40, 66      # ids of the f16x2 tiles with 2 / 3 / 4 LDS stages (csrc/conv_x3.hip)
 
 
 class Act(object):
@@ -72,16 +70,23 @@ def train_fwd_cfg(cfg_id, splitk):
     """(tile configuration, split-K) a table names for a forward convolution -> the pair the training forward launches.  The
     training tables fall back on the inference tables' entries, whose ids include families that cannot give the BatchNorm
     statistics this forward takes from the epilogue:
-      * a k-parity tile (ws + 9 .. ws + 15, round 6): the same tile with one consumer group, split-K kept;
-      * a wave-private small-output tile (small_first_cfg() and up): its split-K counts k-parts inside the workgroup, not
-        workspace splits, and it writes no statistics -- the library's own choice instead, (-1, 0).
+      * a k-parity tile (round 6): the same tile with one consumer group (its stats_twin), split-K kept;
+      * a wave-private small-output tile: its split-K counts k-parts inside the workgroup, not workspace splits, and it writes no
+        statistics -- the library's own choice instead, (-1, 0).
     Data gradients keep the table's ids: they take no statistics, and every family runs them (tests/test_gpu_train_replay.py)."""
-    ws0 = K.ws_first_cfg()
-    if ws0 + 9 <= cfg_id < ws0 + 16:
-        return ws0 + (0, 1, 2, 3, 1, 2, 3)[cfg_id - ws0 - 9], splitk
-    if cfg_id >= K.small_first_cfg():
+    d = conv_cfg(cfg_id) if cfg_id >= 0 else None
+    if d is not None and d.family == 'kparity':
+        return d.stats_twin, splitk
+    if d is not None and d.splitk_mode == 'workgroup':
         return -1, 0
     return cfg_id, splitk
+
+
+def tune_cfgs(f16):
+    """The tile configurations a training forward is measured on: the nine bf16x3 tiles; with the f16x2 operands the f16x2 tiles x
+    {2, 3, 4} LDS stages and the specialised-wave tiles that emit the BatchNorm statistics it takes from the epilogue (no k-parity tile)."""
+    fams = ('f16x2', 'ws', 'ws_pre') if f16 else ('bf16x3',)
+    return [d.id for d in conv_cfgs() if d.family in fams and d.bn_stats == f16]
 
 
 class ModelSettings(object):
@@ -398,13 +403,8 @@ class TrainStep(object):
         # PPYOLO_HIP_TRAIN_RETUNE=1: measure the f16x2 geometries again even where the table has an entry (new candidate kernels)
         again = f16 and os.environ.get('PPYOLO_HIP_TRAIN_RETUNE', '0') == '1' and tkey not in self._measured
         if (ent is None or again) and self.tune:
-            ids = list(range(NUM_FP32_CFGS, NUM_FP32_CFGS + 9))                 # the nine bf16x3 tiles
-            if f16:
-                ids = list(range(NUM_X3_F16_FIRST, NUM_X3_F16_LAST + 1))        # the nine f16x2 tiles x {2, 3, 4} LDS stages
-                ids += list(range(K.ws_first_cfg(), K.ws_first_cfg() + min(9, K.ws_num_cfgs())))      # ... and with specialised waves (csrc/conv_ws.hip;
-                # not the k-parity tiles ws + 9..12 of round 6: they do not emit the BatchNorm statistics the training forward takes from the epilogue)
             best = None
-            for cfg_id in ids:
+            for cfg_id in tune_cfgs(f16):
                 for splitk in (1, 2, 3, 4, 6, 8):
                     if splitk > 1 and chunks // splitk < 4:
                         continue
@@ -481,20 +481,20 @@ class TrainStep(object):
         # BatchNorm statistics from the convolution's epilogue (the f16x2 kernels, one split): saves the
         # statistics kernel's pass over the raw output
         slices = 0
-        s_first = K.stream_first_cfg()
+        on_stream = cfg_id >= 0 and conv_cfg(cfg_id).family == 'stream'
         # Frozen 1x1 layers on the streaming kernel (the HBM-bound conv3 / shortcut layers of stage 2): the raw output is never
         # stored -- one launch for the statistics, one that applies the BatchNorm to its own accumulators (ops.conv1x1_bn_apply)
         epi = (self.bn_epilogue and has_bn and use_f16 and self.fuse_stats and not trainable and not coord and splitk == 1
-               and s_first <= cfg_id < s_first + 2 and (R, S, stride) == (1, 1, 1))
+               and on_stream and (R, S, stride) == (1, 1, 1))
         if (self.bn_epilogue_all and not epi and has_bn and use_f16 and self.fuse_stats and not trainable and not coord and (R, S, stride) == (1, 1, 1)
                 and Cp == 128 and Kout % 128 == 0 and (Kout // 128) & (Kout // 128 - 1) == 0 and Kout // 128 <= 16 and xin.H * xin.W >= 32):
-            epi, cfg_id, splitk = True, s_first, 1          # (the C = 128 layers whatever tile the table names: measured +0.8 %)
+            epi, cfg_id, splitk = True, K.stream_first_cfg(), 1          # (the C = 128 layers whatever tile the table names: measured +0.8 %)
         if epi:
             need = K.conv2d_bn_partials_bytes(xin.N * Ho * Wo, Kout) // 4
             if self._bn_part is None or self._bn_part.numel() < need:
                 self._bn_part = torch.empty(need, dtype=torch.float32, device=self.dev)
-            slices = K.conv1x1_stats(xin.view(), ent['f16'], b0, Kout, cfg_id - s_first, xin.amax, self._bn_part)
-        elif has_bn and use_f16 and self.fuse_stats and splitk == 1 and cfg_id >= NUM_X3_F16_FIRST:      # (every f16x2 kernel family)
+            slices = K.conv1x1_stats(xin.view(), ent['f16'], b0, Kout, conv_cfg(cfg_id).local, xin.amax, self._bn_part)
+        elif has_bn and use_f16 and self.fuse_stats and splitk == 1 and cfg_id >= 0 and conv_cfg(cfg_id).bn_stats:
             need = K.conv2d_bn_partials_bytes(xin.N * Ho * Wo, Kout) // 4
             if self._bn_part is None or self._bn_part.numel() < need:
                 self._bn_part = torch.empty(need, dtype=torch.float32, device=self.dev)
@@ -519,7 +519,7 @@ class TrainStep(object):
             y.amax = self.new_amax(xin.N) if self.f16 else None
             if epi:
                 K.conv1x1_bn_apply(xin.view(), ent['f16'], b0, mean, invstd, self.param(prefix + '.bn.weight'), self.param(prefix + '.bn.bias'),
-                                   y.view(), act, None if res is None else res.view(), cfg_id - s_first, xin.amax, y.amax)
+                                   y.view(), act, None if res is None else res.view(), conv_cfg(cfg_id).local, xin.amax, y.amax)
             else:
                 K.bn_train_apply(raw.view(), mean, invstd, self.param(prefix + '.bn.weight'), self.param(prefix + '.bn.bias'), y.view(), act,
                                  None if res is None else res.view(), y.amax)

@@ -51,8 +51,8 @@ ALLOWLIST = {
     'amax_slots': 'torch reduction (no kernel): the maximum its consumer is scaled by',
 }
 # host-only helpers and types: no launch
-HOST = {'View', 'conv_out_hw', 'dcn_out_hw', 'conv2d_workspace_bytes', 'conv2d_pick', 'stream_first_cfg', 'ws_first_cfg', 'ws_num_cfgs',
-        'small_first_cfg', 'small_num_cfgs', 'patch_first_cfg', 'conv2d_bn_partials_bytes', 'dcnv2_num_configs', 'dcnv2_scheme',
+HOST = {'View', 'conv_out_hw', 'dcn_out_hw', 'conv2d_workspace_bytes', 'conv2d_pick', 'ConvCfg', 'conv_cfg', 'conv_cfgs', 'stream_first_cfg', 'ws_first_cfg',
+        'small_first_cfg', 'patch_first_cfg', 'conv2d_bn_partials_bytes', 'dcnv2_num_configs', 'dcnv2_scheme',
         'dcnv2_configs', 'dcnv2_workspace_bytes', 'matrix_nms_workspace'}
 
 
@@ -128,25 +128,11 @@ def sum_bound(S, t, P):
 
 # ---- conv families -------------------------------------------------------------------------------------------------------
 def conv_family(ops, cfg, f16, x3):
-    """Kernel family a conv cfg id selects (csrc/conv_igemm.hip id ranges)."""
+    """Kernel family a conv cfg id selects (ops.conv_cfg; the f16x2 tile kinds and the two plain kinds of specialised-wave tiles as one each)."""
     if cfg is None or cfg < 0:
         return 'default-f16x2' if f16 else ('default-bf16x3' if x3 else 'default-fp32')
-    s0, p0, w0, sm0 = ops.stream_first_cfg(), ops.patch_first_cfg(), ops.ws_first_cfg(), ops.small_first_cfg()
-    if cfg < 31:
-        return 'fp32'
-    if cfg < 40:
-        return 'bf16x3'
-    if cfg < s0:
-        return 'f16x2'
-    if cfg < p0:
-        return 'stream'
-    if cfg < w0:
-        return 'patch'
-    if cfg < w0 + 9:
-        return 'ws'
-    if cfg < sm0:
-        return 'kparity'
-    return 'small'
+    fam = ops.conv_cfg(cfg).family
+    return {'f16x2_slab': 'f16x2', 'f16x2_tall': 'f16x2', 'ws_pre': 'ws'}.get(fam, fam)
 
 
 def family_units(fam, f16):

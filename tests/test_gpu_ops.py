@@ -62,7 +62,19 @@ def test_conv_units_golden(golden):
 NUM_CFGS = 94      # 31 exact-fp32 MFMA configurations + 9 bf16x3 + 9 f16x2 with 2 LDS stages + 9 with 3 + 9 with 4
                    # + 9 + 9 f16x2 with slab reuse (3x3 / stride 1 / pad 1 only) and 2 / 3 stages
                    # + 3 x 3 f16x2 tiles of 192x128 / 192x256 / 96x256 with 2 / 3 / 4 stages (conv_x3.hip)
-SLAB0, SLAB1 = 67, 85
+SLAB0, SLAB1 = 67, 85      # (the parametrisations below are laid out at collection, before there is a library to ask)
+
+
+def first_cfg(family):
+    """First conv cfg id of a family, from the library's descriptors (ops.conv_cfgs)."""
+    from ppyolo_hip import ops
+    return next(d.id for d in ops.conv_cfgs() if d.family == family)
+
+
+def test_literal_id_ranges_match_the_descriptors():
+    from ppyolo_hip import ops
+    assert [d.id for d in ops.conv_cfgs() if d.family == 'f16x2_slab'] == list(range(SLAB0, SLAB1))
+    assert first_cfg('stream') == NUM_CFGS
 
 
 @pytest.mark.parametrize('cfg', range(NUM_CFGS))
@@ -742,11 +754,12 @@ def test_conv_random_shapes_all_kernels():
                               cfg=cfg, splitk=splitk, ws=ws, w_x3=ops.split_weights_bf16x3(wk),
                               w_f16=ops.split_weights_f16x2(wk, sc.cuda()), amax_in=ops.amax_slots(xd))
         special_ok = True
-        if ops.patch_first_cfg() <= cfg < ops.ws_first_cfg():                # patch kernel: 3x3 / stride 1, C = 32, K = 32 / 64, no shortcut
+        fam = ops.conv_cfg(cfg).family
+        if fam == 'patch':                # patch kernel: 3x3 / stride 1, C = 32, K = 32 / 64, no shortcut
             special_ok = R == 3 and stride == 1 and C == 32 and K in (32, 64) and not use_res and splitk == 1
-        elif ops.stream_first_cfg() <= cfg < ops.patch_first_cfg():          # streaming kernel: 1x1 / stride 1, C = 64 / 128, whole channel slices
+        elif fam == 'stream':          # streaming kernel: 1x1 / stride 1, C = 64 / 128, whole channel slices
             special_ok = R == 1 and stride == 1 and splitk == 1 and H * W >= 32 and ((C == 64 and K in (32 * 2, 128, 256)) or (C == 128 and K in (128, 256)))
-        if (SLAB0 <= cfg < SLAB1 and not (R == 3 and stride == 1)) or not special_ok:        # refused loudly, no silent other kernel
+        if (fam == 'f16x2_slab' and not (R == 3 and stride == 1)) or not special_ok:        # refused loudly, no silent other kernel
             from ppyolo_hip._lib import PPYoloHipError
             with pytest.raises(PPYoloHipError):
                 run()
@@ -1105,7 +1118,7 @@ def test_specialised_wave_tiles_are_bit_identical_to_the_f16x2_tiles():
     from ppyolo_hip import ops
     first = ops.ws_first_cfg()
     from ppyolo_hip._lib import lib
-    nws = ops.ws_num_cfgs()          # (behind them: the small-output tiles of csrc/conv_small.hip, test_small_output_tiles_*)
+    nws = sum(d.family in ('ws', 'ws_pre', 'kparity') for d in ops.conv_cfgs())          # (behind them: the small-output tiles of csrc/conv_small.hip, test_small_output_tiles_*)
     g = torch.Generator().manual_seed(4400)
     ws = torch.empty(16 << 20).cuda()
     for N, H, W, C, K, R, stride, res, splitk in ((2, 19, 19, 64, 136, 3, 1, True, 1), (1, 1, 1, 32, 40, 3, 1, False, 1), (3, 1, 7, 64, 72, 1, 1, True, 2),
@@ -1161,7 +1174,7 @@ def test_small_output_tiles_are_bit_identical_to_the_f16x2_tiles():
     shorter than the request depth, more k-parts asked for than waves / chunks."""
     from ppyolo_hip import ops
     first = ops.small_first_cfg()
-    assert ops.small_num_cfgs() == 4
+    assert [d.id for d in ops.conv_cfgs() if d.family == 'small'] == list(range(first, first + 4))
     NW = (4, 4, 8, 8)
     g = torch.Generator().manual_seed(6100)
     ws = torch.empty(16 << 20).cuda()
@@ -1224,7 +1237,7 @@ def test_small_output_tiles_read_and_write_presplit_tensors():
     k-parts too -- a tile kernel cannot split there) and as the PRODUCER of such a tensor, against a tile kernel in the same place: equal
     outputs for one k-part, fp32 rounding between different part counts; the stored scales are the tile's."""
     from ppyolo_hip import ops
-    first, f0 = ops.small_first_cfg(), 40
+    first, f0 = ops.small_first_cfg(), first_cfg('f16x2')
     g = torch.Generator().manual_seed(6200)
     for C, Km, K2, H, R2, stride in ((256, 128, 256, 19, 3, 1), (512, 64, 96, 12, 3, 2), (64, 256, 128, 16, 1, 1)):
         N = 3
@@ -1324,7 +1337,7 @@ def test_conv3x3_conv1x1_matches_two_launches_and_fp64(N, H, W, pool):
     AvgPool2d(2, 2) of the output is written too -- bit-equal to (((a + b) + c) + d) * 0.25 of the y the same launch stored."""
     from ppyolo_hip import ops
     g = torch.Generator().manual_seed(23 + H)
-    f0 = 40
+    f0 = first_cfg('f16x2')
     C = 256
     x = torch.relu(torch.randn(N, H, W, C, generator=g))
     if N > 1:
@@ -1483,7 +1496,7 @@ def test_presplit_pair_matches_fp64_as_well_as_the_plain_pair():
     reads / writes such tensors, images of very different magnitude in one batch, an all-zero image."""
     from ppyolo_hip import ops
     g = torch.Generator().manual_seed(17)
-    f0 = 40                                  # first f16x2 tile id
+    f0 = first_cfg('f16x2')
     w0 = ops.ws_first_cfg()
     cases = [dict(C=256, Km=128, K2=256, H=19, stride=1, act='leaky', posb=True, pcfg=f0 + 4, ccfg=f0 + 2),
              dict(C=512, Km=128, K2=128, H=24, stride=2, act='relu', posb=False, pcfg=w0 + 2, ccfg=w0 + 8),
@@ -1614,7 +1627,7 @@ def test_presplit_chain_bounds_from_the_tracked_maximum():
     from ppyolo_hip import ops
     g = torch.Generator().manual_seed(23)
     N, H, chans, ks = 2, 19, [512, 256, 512, 256, 512], [1, 3, 1, 3]
-    f0, w0 = 40, ops.ws_first_cfg()
+    f0, w0 = first_cfg('f16x2'), ops.ws_first_cfg()
     cfgs = [f0 + 4, w0 + 1, f0 + 16, w0 + 0]
     x = torch.relu(torch.randn(N, H, H, chans[0], generator=g))
     x[1] *= 40.0

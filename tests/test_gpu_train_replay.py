@@ -89,7 +89,6 @@ def _assert_covered(rep, chosen):
     for r in rep.census:
         if r.get('kind') in ('fwd', 'fwd-stats', 'fwd-apply', 'dgrad') and r['op'] != 'stem_conv':
             by.setdefault(('dgrad' if r['kind'] == 'dgrad' else 'fwd', _key_of(r)), []).append(r)
-    s_first = ops.stream_first_cfg()
     missing = []
     for kind, key, c, s in chosen:
         recs = by.get((kind, key), [])
@@ -97,7 +96,7 @@ def _assert_covered(rep, chosen):
         ok = any((r['cfg'], r['splitk']) == want for r in recs)
         if kind == 'fwd' and not ok:
             # the frozen C = 128 1x1 layers go to the streaming kernel whatever tile the table names (train.py: bn_epilogue_all)
-            ok = ':C128:' in key and key.endswith(':R1:s1') and any(r['family'] == 'stream' and r['cfg'] in (s_first, s_first + 1)
+            ok = ':C128:' in key and key.endswith(':R1:s1') and any(r['family'] == 'stream' and ops.conv_cfg(r['cfg']).family == 'stream'
                                                                    and r['splitk'] == 1 for r in recs)
         if not ok:
             missing.append((kind, key, c, s, [(r['cfg'], r['splitk'], r['family']) for r in recs]))
@@ -130,9 +129,9 @@ def test_train_step_launch_replay(name, cfgc, S, N, freeze_at, monkeypatch):
         assert {'wgrad-nine-tap-f16x2', 'wgrad-x3-f16x2'} <= wg, wg
     if name == 'r50_608_n8_fa3':
         assert any(f == 'kparity' for f, _ in dg), dg
-        ws0 = ops.ws_first_cfg()
-        assert any(k == 'fwd' and ws0 + 9 <= c < ws0 + 16 for k, _, c, _ in chosen), 'no forward id remapped from k-parity'
-        if any(k == 'dgrad' and ws0 <= c < ws0 + 9 for k, _, c, _ in chosen):
+        fam_of = lambda c: ops.conv_cfg(c).family if c >= 0 else None
+        assert any(k == 'fwd' and fam_of(c) == 'kparity' for k, _, c, _ in chosen), 'no forward id remapped from k-parity'
+        if any(k == 'dgrad' and fam_of(c) in ('ws', 'ws_pre') for k, _, c, _ in chosen):
             assert any(f == 'ws' for f, _ in dg), dg
         ops_seen = {r['op'] for r in rep.census}
         assert {'zero_insert', 'dcnv2_backward', 'dcnv2'} <= ops_seen, ops_seen

@@ -56,11 +56,39 @@ def test_train_fwd_cfg_maps_every_table_entry(K):
 def test_train_fwd_cfg_rules(K):
     from ppyolo_hip.train import train_fwd_cfg
     ws0, sm0 = K.ws_first_cfg(), K.small_first_cfg()
-    assert sm0 == ws0 + 16 and K.small_num_cfgs() == 4
+    assert sm0 == ws0 + 16 and len(K.conv_cfgs()) == sm0 + 4
     assert train_fwd_cfg(ws0 + 9, 4) == (ws0 + 0, 4)          # k-parity 128x128 -> the same tile with one consumer group
     assert train_fwd_cfg(ws0 + 15, 1) == (ws0 + 3, 1)
-    for c in range(sm0, sm0 + K.small_num_cfgs()):
+    for c in range(sm0, sm0 + 4):
         for s in (1, 2, 4):
             assert train_fwd_cfg(c, s) == (-1, 0)            # a small-output tile: no statistics, k-parts not splits
     for c in (-1, 40, 66, ws0, ws0 + 8):
         assert train_fwd_cfg(c, 2) == (c, 2)
+
+
+def _old_rule(K, cfg, splitk):
+    """train_fwd_cfg as it stood before the library described its ids, range by range."""
+    ws0 = K.ws_first_cfg()
+    if ws0 + 9 <= cfg < ws0 + 16:
+        return ws0 + (0, 1, 2, 3, 1, 2, 3)[cfg - ws0 - 9], splitk
+    if cfg >= K.small_first_cfg():
+        return -1, 0
+    return cfg, splitk
+
+
+def test_train_fwd_cfg_matches_the_range_rule(K):
+    from ppyolo_hip.train import train_fwd_cfg
+    pairs = [(c, s) for c in range(-1, len(K.conv_cfgs())) for s in (1, 2, 4)]
+    for path, _ in _tables():
+        with open(path) as fh:
+            pairs += [(ent[0], ent[1]) for key, ent in json.load(fh).items() if key.startswith('conv:')]
+    assert len(pairs) > 700
+    for c, s in pairs:
+        assert train_fwd_cfg(c, s) == _old_rule(K, c, s), (c, s)
+
+
+def test_training_tune_candidates(K):
+    from ppyolo_hip.train import tune_cfgs
+    ws0 = K.ws_first_cfg()
+    assert tune_cfgs(False) == list(range(31, 40))
+    assert tune_cfgs(True) == list(range(40, 67)) + [ws0 + i for i in range(9)]

@@ -21,7 +21,8 @@ for (N, H, C, K) in ((8, 38, 256, 1024), (8, 76, 128, 512), (8, 19, 512, 2048)):
     am = ops.amax_slots(x)
     res = []
     first = ops.stream_first_cfg()
-    for cfg in list(range(40, 67)) + list(range(85, 94)) + [first, first + 1] + list(range(ops.ws_first_cfg(), ops.ws_first_cfg() + 12)):
+    ws12 = [d.id for d in ops.conv_cfgs() if d.family in ('ws', 'ws_pre', 'kparity')][:12]
+    for cfg in [d.id for d in ops.conv_cfgs() if d.family in ('f16x2', 'f16x2_tall')] + [first, first + 1] + ws12:
         def run():
             ops.conv2d_bn_act(ops.View(x), wk, sc, sh, ops.View(y), 1, 0, 'relu', residual=ops.View(r), cfg=cfg, splitk=1, w_f16=wf, amax_in=am,
                               amax_out=ops.amax_slots(N=N, device=y.device))
