@@ -35,6 +35,7 @@ extern "C" {
 #define PPY_ERR_UNSUPPORTED (-2)  /* valid request outside what the kernels implement     */
 #define PPY_ERR_WORKSPACE (-3)    /* workspace missing or too small                       */
 #define PPY_ERR_LAUNCH (-4)       /* hipLaunch / hipFuncSetAttribute failed               */
+#define PPY_ERR_CORRUPT (-5)      /* input data (a JPEG file) damaged or truncated        */
 
 #define PPY_ACT_NONE 0
 #define PPY_ACT_RELU 1
@@ -597,6 +598,70 @@ int ppy_conv3x3_conv1x1_f32(const float *x_split, int x_ld, const float *xscale,
  * These two calls are the only ones of the library that create or destroy state; they synchronise nothing. */
 int ppy_lane_stream_create(void **stream, const uint32_t *h_cu_mask, int mask_words);
 int ppy_lane_stream_destroy(void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Baseline JPEG decoding, bit for bit with libjpeg-turbo's defaults -- JDCT_ISLOW inverse DCT, fancy upsampling, integer YCbCr
+ * tables -- i.e. the pixels of cv2.imread(path) / cv2.imdecode(buf, 1) (reference demo.py:41, tools/cocotools.py:105,
+ * tools/transform.py:87), delivered as the uint8 HWC BGR device images ppy_preprocess_u8_f32 takes.  DESIGN.md section 10.
+ *
+ * Accepted: SOF0 / SOF1 (Huffman, 8-bit samples), one interleaved scan, 1 component (grey, replicated to B = G = R) or 3
+ * (YCbCr) with chroma 1x1 and luma 1x1, 2x1 or 2x2; 8- and 16-bit quantisation tables; restart intervals; any APPn / COM
+ * segments and 0xFF fill bytes.  Everything else that is a valid file -- progressive, arithmetic, lossless, 12-bit, 4
+ * components, RGB (Adobe transform 0), other sampling factors, several scans -- returns PPY_ERR_UNSUPPORTED, and a file that
+ * is damaged or ends early returns PPY_ERR_CORRUPT (libjpeg would fill the rest with grey and warn); both with a reason
+ * string.  No input makes these functions read or write outside the buffers they are given.
+ *
+ * The seam between host and device is the COEFFICIENT BUFFER: int16, per component [block row][block column][64], block
+ * counts those of whole MCUs, quantised values as coded, stored TRANSPOSED inside a block (index column * 8 + row; the
+ * quant tables of the descriptor in the same order).  ppy_jpeg_info and ppy_jpeg_entropy_decode are plain host code: no
+ * GPU call, no state, safe to call from any number of threads, one call per image.  All pointers of the first five
+ * functions are HOST pointers.
+ *
+ * A batch: for each image ppy_jpeg_info -> coef_bytes; place the images' coefficients in one host buffer at offsets that
+ * are multiples of 16 (desc.coef_base, set by the caller BEFORE or after the decode; it is preserved);
+ * ppy_jpeg_entropy_decode each (it zeroes its part first); ppy_jpeg_pack_table writes the device descriptor table
+ * (ppy_jpeg_table_bytes(n) bytes) for the output pointers into host memory; copy table and coefficients to the device
+ * (one copy when they share a pinned buffer); ppy_jpeg_reconstruct_u8 enqueues TWO launches for the whole batch, whatever
+ * the number and sizes of the images (inverse DCT into block-padded planes in the workspace; upsample + colour +
+ * orientation + store).  out[i]: device uint8 [out_height][row_stride[i] bytes], pixel (y, x) channel c at
+ * y * row_stride + 3 * x + c, row_stride >= 3 * out_width, any alignment.  apply_orientation != 0 applies the EXIF
+ * orientation (1..8) as cv2.imread does; 0 delivers the stored raster (cv2.IMREAD_IGNORE_ORIENTATION).
+ * ws: ppy_jpeg_workspace_bytes(n, descs) bytes (0 = a descriptor is invalid), 16-byte aligned; table and coef 16-byte
+ * aligned.  TRUST BOUNDARY: h_descs and apply_orientation are validated on the host (geometry, coefficient ranges against
+ * coef_bytes, workspace size) and size the grids; the kernels read the device table, including the output pointers and row
+ * strides, WITHOUT further checks.  The table must be the one ppy_jpeg_pack_table wrote from these very descriptors with the
+ * same apply_orientation, unmodified; a call that never synchronises cannot verify device memory. */
+typedef struct ppy_jpeg_info_t {
+    int status;                       /* the return value again */
+    int width, height;                /* as stored in the file */
+    int out_width, out_height;        /* after the EXIF orientation */
+    int orientation;                  /* 1..8; 1 when the file has none */
+    int components;                   /* 1 or 3 */
+    int h_samp[3], v_samp[3];         /* sampling factors (1 x 1 for a grey file) */
+    int blocks_w[3], blocks_h[3];     /* 8x8 blocks per row / column of each component */
+    int restart_interval;             /* MCUs, 0 = none */
+    long long coef_bytes;             /* size of the image's coefficients */
+    char reason[64];                  /* why status != PPY_OK */
+} ppy_jpeg_info_t;
+typedef struct ppy_jpeg_desc_t {
+    int width, height, components, orientation;
+    int h_samp[3], v_samp[3];
+    int blocks_w[3], blocks_h[3];
+    long long coef_offset[3];         /* int16 elements from the start of the image's coefficients */
+    long long coef_bytes;
+    long long coef_base;              /* CALLER: byte offset of the image's coefficients in the batch buffer, % 16 == 0 */
+    unsigned short quant[3][64];      /* per component, stored (transposed) order */
+} ppy_jpeg_desc_t;
+int ppy_jpeg_info(const unsigned char *h_data, size_t bytes, ppy_jpeg_info_t *h_info);
+/* h_reason: NULL or 64 chars. */
+int ppy_jpeg_entropy_decode(const unsigned char *h_data, size_t bytes, int16_t *h_coef, size_t coef_bytes,
+                            ppy_jpeg_desc_t *h_desc, char *h_reason);
+size_t ppy_jpeg_workspace_bytes(int n, const ppy_jpeg_desc_t *h_descs);
+size_t ppy_jpeg_table_bytes(int n);
+int ppy_jpeg_pack_table(int n, const ppy_jpeg_desc_t *h_descs, unsigned char *const *h_out, const long long *h_row_stride,
+                        int apply_orientation, void *h_table, size_t table_bytes);
+int ppy_jpeg_reconstruct_u8(int n, const ppy_jpeg_desc_t *h_descs, int apply_orientation, const void *table, const int16_t *coef,
+                            size_t coef_bytes, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@ class Decode(object):
         # reference :32-37: eval target size unless for_test
         self.target_size = (cfg.test_cfg if for_test else cfg.eval_cfg)['target_size']
         self._pre = None
+        self._jpeg = None
 
     def _preprocessor(self):
         if self._pre is None:
@@ -38,6 +39,15 @@ class Decode(object):
         pimage, im_size = self._preprocessor()(images)
         preds = self._yolo(pimage, im_size)
         return [self._split(p.cpu().detach().numpy()) for p in preds]
+
+    def detect_files(self, paths_or_bytes):
+        """demo.py's loop from the files themselves: JPEG paths / byte strings -> decoded on the device
+        (ppyolo_hip/jpeg.py, the pixels cv2.imread gives) -> detect_raw.  A file outside the decoder's subset raises
+        PPYoloHipError naming the reason."""
+        if self._jpeg is None:
+            from ppyolo_hip.jpeg import JpegDecoder
+            self._jpeg = JpegDecoder()
+        return self.detect_raw(self._jpeg.decode(list(paths_or_bytes)))
 
     def predict(self, image, im_size):
         """numpy [N,3,S,S] f32 + numpy [N,2] (h, w) -> list of numpy [K,6] f32."""

@@ -30,6 +30,21 @@ class ConvCfgInfo(ctypes.Structure):
                                      'writes_presplit', 'bn_stats', 'stats_twin')]
 
 
+class JpegInfo(ctypes.Structure):
+    """ppy_jpeg_info_t (include/ppyolo_hip.h)."""
+    _fields_ = [('status', c_int), ('width', c_int), ('height', c_int), ('out_width', c_int), ('out_height', c_int),
+                ('orientation', c_int), ('components', c_int), ('h_samp', c_int * 3), ('v_samp', c_int * 3),
+                ('blocks_w', c_int * 3), ('blocks_h', c_int * 3), ('restart_interval', c_int), ('coef_bytes', c_longlong),
+                ('reason', ctypes.c_char * 64)]
+
+
+class JpegDesc(ctypes.Structure):
+    """ppy_jpeg_desc_t (include/ppyolo_hip.h)."""
+    _fields_ = [('width', c_int), ('height', c_int), ('components', c_int), ('orientation', c_int), ('h_samp', c_int * 3),
+                ('v_samp', c_int * 3), ('blocks_w', c_int * 3), ('blocks_h', c_int * 3), ('coef_offset', c_longlong * 3),
+                ('coef_bytes', c_longlong), ('coef_base', c_longlong), ('quant', (ctypes.c_ushort * 64) * 3)]
+
+
 _PROTOS = {
     'ppy_version': (c_int, []),
     'ppy_error_string': (ctypes.c_char_p, [c_int]),
@@ -139,6 +154,13 @@ _PROTOS = {
                                          c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 6 + [c_float, c_float, c_void_p, c_void_p]),
     'ppy_lane_stream_create': (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_uint32), c_int]),
     'ppy_lane_stream_destroy': (c_int, [c_void_p]),
+    'ppy_jpeg_info': (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegInfo)]),
+    'ppy_jpeg_entropy_decode': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(JpegDesc), c_void_p]),
+    'ppy_jpeg_workspace_bytes': (c_size_t, [c_int, ctypes.POINTER(JpegDesc)]),
+    'ppy_jpeg_table_bytes': (c_size_t, [c_int]),
+    'ppy_jpeg_pack_table': (c_int, [c_int, ctypes.POINTER(JpegDesc), ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_int,
+                                    c_void_p, c_size_t]),
+    'ppy_jpeg_reconstruct_u8': (c_int, [c_int, ctypes.POINTER(JpegDesc), c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
 }
 
 

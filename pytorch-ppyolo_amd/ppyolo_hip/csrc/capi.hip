@@ -10,6 +10,7 @@ extern "C" const char *ppy_error_string(int code) {
         case PPY_ERR_UNSUPPORTED: return "unsupported configuration";
         case PPY_ERR_WORKSPACE: return "workspace missing or too small";
         case PPY_ERR_LAUNCH: return "HIP launch failed";
+        case PPY_ERR_CORRUPT: return "corrupt or truncated input data";
     }
     return "unknown error";
 }

@@ -1,0 +1,189 @@
+"""JPEG files -> uint8 HWC BGR device tensors, the pixels cv2.imread / cv2.imdecode(buf, 1) give (reference demo.py:41,
+tools/cocotools.py:105, tools/transform.py:87), bit for bit with libjpeg-turbo's defaults.
+
+Host: marker parsing + Huffman decoding into coefficient blocks, plain C++ in the library (csrc/jpeg.hip), one call per image
+on a thread pool -- ctypes releases the GIL.  Device: everything per pixel, two launches per batch (ops are in the library,
+there is no fallback).  The coefficients are written straight into one of two pinned staging buffers and cross to the device
+in one copy together with the descriptor table, so the entropy stage of the next batch overlaps the copy and the kernels of
+this one.
+
+Baseline Huffman JPEG only (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0): anything else raises PPYoloHipError naming the reason, so a
+caller can hand that file to a decoder of its own.  A truncated or damaged file is an error too (libjpeg would fill the
+missing part with grey and warn)."""
+import ctypes
+import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+
+import torch
+
+from . import _lib
+from ._lib import PPYoloHipError, check, lib
+
+MAX_THREADS = 16
+
+
+def _bytes(item):
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    if isinstance(item, (str, os.PathLike)):
+        with open(item, 'rb') as fh:
+            return fh.read()
+    raise PPYoloHipError('expected bytes, a memoryview or a path, got %s' % type(item).__name__)
+
+
+def _refuse(i, rc, reason):
+    kind = {-2: 'unsupported JPEG', -5: 'corrupt JPEG'}.get(rc, lib().ppy_error_string(rc).decode())
+    return PPYoloHipError('item %d: %s: %s (code %d)' % (i, kind, reason.decode(errors='replace') or '?', rc))
+
+
+class HostBatch(object):
+    """Output of the entropy stage: descriptors + the pinned buffer holding [descriptor table | coefficients].  It OWNS one of
+    the decoder's two staging buffers until it is passed to reconstruct() (which may be repeated until a later batch takes the
+    buffer) or release()d; see JpegDecoder.entropy_decode."""
+    __slots__ = ('n', 'descs', 'sizes', 'stage', 'slot', 'gen', 'table_bytes', 'total_bytes')
+
+
+class JpegDecoder(object):
+    def __init__(self, device='cuda', threads=None, apply_orientation=True, max_pixels=1 << 28):
+        """threads: workers of the entropy stage, default min(16, images of the call); never more than 16, never derived from
+        the machine's CPU count.  apply_orientation=False delivers the stored raster (cv2.IMREAD_IGNORE_ORIENTATION).
+        max_pixels: a header that claims more is refused before any buffer is sized from it (a few bytes can claim 65535 x 65535)."""
+        self.max_pixels = int(max_pixels)
+        self.device = torch.device(device)
+        if threads is not None and threads < 1:
+            raise PPYoloHipError('threads must be >= 1')
+        self.threads = None if threads is None else min(int(threads), MAX_THREADS)
+        self.apply_orientation = bool(apply_orientation)
+        self._pool = None
+        self._stage = [None, None]      # pinned uint8 buffers, used in turn
+        self._busy = [None, None]       # event recorded after the copy out of each
+        self._held = [False, False]     # handed out in a HostBatch that has not been reconstructed or released yet
+        self._gen = [0, 0]              # how many batches each buffer has been handed to
+        self._turn = 0
+        self._lock = threading.Lock()   # entropy_decode and reconstruct may run on two threads
+
+    # ---- host stage ---------------------------------------------------------------------------------------------------
+    def _staging(self, nbytes):
+        with self._lock:
+            s = self._turn if not self._held[self._turn] else self._turn ^ 1
+            if self._held[s]:
+                raise PPYoloHipError('both staging buffers belong to batches that wait for reconstruct(): the entropy stage may '
+                                     'run at most two batches ahead; reconstruct() or release() one first')
+            self._held[s] = True
+            self._gen[s] += 1
+            gen = self._gen[s]
+            self._turn = s ^ 1
+            busy, self._busy[s] = self._busy[s], None
+        if busy is not None:                    # the last copy out of this buffer
+            busy.synchronize()
+        if self._stage[s] is None or self._stage[s].numel() < nbytes:
+            t = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8)
+            self._stage[s] = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
+        return s, gen, self._stage[s]
+
+    def release(self, hb):
+        """Give back the staging buffer of a HostBatch that will not be reconstructed."""
+        with self._lock:
+            if self._gen[hb.slot] == hb.gen:
+                self._held[hb.slot] = False
+
+    def _map(self, fn, n):
+        workers = min(self.threads or MAX_THREADS, n)
+        if workers <= 1:
+            return [fn(i) for i in range(n)]
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max_workers=self.threads or MAX_THREADS, thread_name_prefix='ppy-jpeg')
+        return list(self._pool.map(fn, range(n)))
+
+    def entropy_decode(self, items):
+        """Host only: parse and Huffman-decode every item into a pinned staging buffer.  The returned HostBatch owns that buffer
+        until reconstruct(hb) or release(hb); there are two buffers, so at most two batches can wait at a time (a third call
+        raises instead of overwriting one).  May run on another thread than reconstruct()."""
+        L = lib()
+        datas = [_bytes(it) for it in items]
+        n = len(datas)
+        if n == 0:
+            raise PPYoloHipError('empty batch')
+        descs = (_lib.JpegDesc * n)()
+        sizes = []
+        table_bytes = L.ppy_jpeg_table_bytes(n)
+        total = table_bytes
+        for i, d in enumerate(datas):
+            info = _lib.JpegInfo()
+            rc = L.ppy_jpeg_info(d, len(d), ctypes.byref(info))
+            if rc != _lib.OK:
+                raise _refuse(i, rc, info.reason)
+            if info.width * info.height > self.max_pixels:
+                raise PPYoloHipError('item %d: %d x %d pixels is over max_pixels = %d' % (i, info.width, info.height, self.max_pixels))
+            descs[i].coef_base = total - table_bytes
+            total += (info.coef_bytes + 15) // 16 * 16
+            sizes.append((info.height, info.width, info.out_height, info.out_width, info.coef_bytes))
+        slot, gen, stage = self._staging(total)
+        hb = HostBatch()
+        hb.n, hb.descs, hb.sizes, hb.stage, hb.slot, hb.gen, hb.table_bytes, hb.total_bytes = n, descs, sizes, stage, slot, gen, table_bytes, total
+        base = stage.data_ptr() + table_bytes
+
+        def one(i):
+            reason = ctypes.create_string_buffer(64)
+            rc = L.ppy_jpeg_entropy_decode(datas[i], len(datas[i]), base + descs[i].coef_base, sizes[i][4], ctypes.byref(descs[i]), reason)
+            return rc, reason.value
+
+        try:
+            for i, (rc, reason) in enumerate(self._map(one, n)):
+                if rc != _lib.OK:
+                    raise _refuse(i, rc, reason)
+        except BaseException:
+            self.release(hb)
+            raise
+        return hb
+
+    # ---- device stage -------------------------------------------------------------------------------------------------
+    def reconstruct(self, hb, out=None):
+        """Copy a HostBatch to the device and enqueue the two reconstruction launches on the current stream.  out: optional
+        list of uint8 device tensors [h,w,3] to fill (pixel stride 3, any row stride)."""
+        L = lib()
+        n = hb.n
+        ori = self.apply_orientation
+        shapes = [(s[2], s[3]) if ori else (s[0], s[1]) for s in hb.sizes]
+        if out is None:
+            out = [torch.empty((h, w, 3), dtype=torch.uint8, device=self.device) for h, w in shapes]
+        if len(out) != n:
+            raise PPYoloHipError('%d output tensors for %d images' % (len(out), n))
+        for t, (h, w) in zip(out, shapes):
+            if not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w, 3) or t.stride(2) != 1 or t.stride(1) != 3 \
+                    or (h > 1 and t.stride(0) < 3 * w):
+                raise PPYoloHipError('output must be a uint8 device tensor [%d, %d, 3] with pixel stride 3' % (h, w))
+        with self._lock:
+            if self._gen[hb.slot] != hb.gen:
+                raise PPYoloHipError('stale HostBatch: its staging buffer has been handed to a later batch')
+            self._held[hb.slot] = True          # (again, when the same batch is reconstructed a second time)
+            busy = self._busy[hb.slot]
+        if busy is not None:                    # the same HostBatch again: its last copy still reads the table
+            busy.synchronize()
+        check(L.ppy_jpeg_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
+                                    (ctypes.c_longlong * n)(*[max(t.stride(0), 3 * t.shape[1]) for t in out]), int(ori),
+                                    hb.stage.data_ptr(), hb.table_bytes), 'ppy_jpeg_pack_table')
+        blob = torch.empty(hb.total_bytes, dtype=torch.uint8, device=self.device)
+        blob.copy_(hb.stage[:hb.total_bytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        with self._lock:
+            self._busy[hb.slot] = ev
+            self._held[hb.slot] = False
+        ws_bytes = L.ppy_jpeg_workspace_bytes(n, hb.descs)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
+        check(L.ppy_jpeg_reconstruct_u8(n, hb.descs, int(ori), blob.data_ptr(), blob.data_ptr() + hb.table_bytes, hb.total_bytes - hb.table_bytes,
+                                        ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream), 'ppy_jpeg_reconstruct_u8')
+        return out
+
+    # ---- the user's calls ---------------------------------------------------------------------------------------------
+    def decode(self, items, out=None):
+        """list of bytes / memoryview / paths -> list of uint8 [h,w,3] BGR device tensors, asynchronous on the current stream."""
+        return self.reconstruct(self.entropy_decode(items), out=out)
+
+    def imdecode(self, buf):
+        return self.decode([buf])[0]
+
+    def imread(self, path):
+        return self.decode([path])[0]

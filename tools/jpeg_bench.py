@@ -1,0 +1,203 @@
+"""JPEG decoder timings (ppyolo_hip/jpeg.py, csrc/jpeg.hip).
+
+    python tools/jpeg_bench.py [--bs 8] [--window 1.0] [--rounds 5] [--no-model]
+
+Input: the COCO-sized files of tests/golden/g20_jpeg.npz replicated to a batch.  Reports
+  entropy_ms_per_image   host stage (parse + Huffman) at 1 and 16 threads, wall clock over 4 batches per call;
+  h2d                    bytes and time (device events) of the one copy per batch: descriptor table + coefficients;
+  reconstruct            the two kernels as the mean of graph-replayed launches, beside a device-to-device copy moving the
+                         same number of bytes (coefficients read + pixels written), replayed the same way: the roofline;
+  detect                 files -> detections images/s at R50vd-608 with the decoder on a producer thread and a stream of its
+                         own, one batch ahead, beside detect_raw on the same images already decoded, alternating in one run;
+                         and, to attribute a gap, detect_raw beside the entropy stage alone and beside copy + kernels alone;
+  pillow_ms_per_image    Pillow's (libjpeg-turbo's) decode of the same files at 1 and 16 threads, where Pillow is installed.
+Every timed window lasts at least --window seconds (the repeat count is calibrated first); the detect legs alternate for
+--rounds rounds and report every round, so the spread is in the output.  One JSON line."""
+import argparse
+import io
+import json
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'pytorch-ppyolo_amd'), os.path.join(ROOT, 'tests')]
+
+from ppyolo_hip import _lib  # noqa: E402
+from ppyolo_hip.jpeg import JpegDecoder  # noqa: E402
+
+
+def files(bs):
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'g20_jpeg.npz'))
+    big = [g['jpg_' + str(n)].tobytes() for n in g['names'] if str(n).startswith('coco_')]
+    return [big[i % len(big)] for i in range(bs)]
+
+
+def wall_s(fn, window):
+    """Seconds per call of a host function, over at least `window` seconds."""
+    fn()
+    n, t0 = 0, time.perf_counter()
+    while n < 3 or time.perf_counter() - t0 < window:
+        fn()
+        n += 1
+    return (time.perf_counter() - t0) / n
+
+
+def event_ms(fn, window):
+    """Device time per call of `fn` (events around a loop that lasts at least `window` seconds)."""
+    def run(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(iters):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) / iters
+    fn()
+    torch.cuda.synchronize()
+    one = max(run(50), 1e-4)
+    return run(max(int(window * 1e3 / one), 50))
+
+
+def replay_ms(fn, window):
+    """Mean time of `fn`'s launches replayed from a captured graph."""
+    fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return event_ms(g.replay, window)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--bs', type=int, default=8)
+    ap.add_argument('--window', type=float, default=1.0)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--no-model', action='store_true')
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs a ROCm device'
+    data = files(a.bs)
+    L = _lib.lib()
+    res = dict(bs=a.bs, device=torch.cuda.get_device_name(0), file_bytes=sum(len(d) for d in data))
+
+    # host stage
+    res['entropy_ms_per_image'] = {}
+    for th in (1, 16):
+        jd = JpegDecoder(threads=th)
+        many = data * 4
+        res['entropy_ms_per_image'][str(th)] = wall_s(lambda: jd.release(jd.entropy_decode(many)), a.window) * 1e3 / len(many)
+
+    # copy + kernels
+    jd = JpegDecoder()
+    hb = jd.entropy_decode(data)
+    outs = jd.reconstruct(hb)
+    torch.cuda.synchronize()
+    pixel_bytes = sum(t.numel() for t in outs)
+    coef_bytes = hb.total_bytes - hb.table_bytes
+    blob = torch.empty(hb.total_bytes, dtype=torch.uint8, device='cuda')
+    res['h2d'] = dict(bytes=hb.total_bytes, ms=event_ms(lambda: blob.copy_(hb.stage[:hb.total_bytes], non_blocking=True), a.window))
+    ws_bytes = L.ppy_jpeg_workspace_bytes(hb.n, hb.descs)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device='cuda')
+
+    def kernels():
+        _lib.check(L.ppy_jpeg_reconstruct_u8(hb.n, hb.descs, 1, blob.data_ptr(), blob.data_ptr() + hb.table_bytes, coef_bytes, ws.data_ptr(),
+                                             ws_bytes, torch.cuda.current_stream().cuda_stream), 'ppy_jpeg_reconstruct_u8')
+    half = (coef_bytes + pixel_bytes) // 2
+    src, dst = torch.empty(half, dtype=torch.uint8, device='cuda'), torch.empty(half, dtype=torch.uint8, device='cuda')
+    k_ms, c_ms = replay_ms(kernels, a.window), replay_ms(lambda: dst.copy_(src), a.window)
+    res['reconstruct'] = dict(ms=k_ms, coef_bytes=coef_bytes, pixel_bytes=pixel_bytes, plane_bytes=ws_bytes,
+                              copy_same_bytes_ms=c_ms, images_per_s=a.bs / k_ms * 1e3)
+
+    # files -> detections, beside pre-decoded pixels -> detections
+    if not a.no_model:
+        from conftest import build_model
+        from config import PPYOLO_2x_Config
+        from model.decode_np import Decode
+        cfg = PPYOLO_2x_Config()
+        model, _ = build_model(cfg, 0, 'cuda')
+        dec = Decode(model, ['c%d' % i for i in range(80)], True, cfg, for_test=True)
+        pixels = [t.clone() for t in outs]
+        producer = ThreadPoolExecutor(1)
+
+        def raw_fed(n):
+            for _ in range(n):
+                dec.detect_raw(pixels)
+
+        side = torch.cuda.Stream()
+        jd_dev = JpegDecoder()
+        fixed = jd_dev.entropy_decode(data)   # (a decoder of its own: nothing else writes its staging buffer)
+
+        def produce_all():                    # the whole decode, one batch ahead, on a stream of its own
+            with torch.cuda.stream(side):
+                imgs = jd.decode(data)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return imgs, ev
+
+        def produce_host_only():              # attribution: the entropy stage alone beside the model (its output is dropped)
+            jd_host.release(jd_host.entropy_decode(data))
+            return pixels, None
+
+        def produce_device_only():            # attribution: copy + kernels alone, from one fixed host batch
+            with torch.cuda.stream(side):
+                imgs = jd_dev.reconstruct(fixed)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return imgs, ev
+
+        def fed(produce):
+            def run(n):
+                fut = producer.submit(produce)
+                for _ in range(n):
+                    imgs, ev = fut.result()
+                    fut = producer.submit(produce)
+                    if ev is not None:
+                        torch.cuda.current_stream().wait_event(ev)
+                    dec.detect_raw(imgs)      # ends in a host synchronise, so imgs are free when they are dropped
+                fut.result()
+                torch.cuda.synchronize()
+            return run
+        jd_host = JpegDecoder()
+        legs = [('raw', raw_fed), ('files', fed(produce_all)), ('raw_beside_entropy_stage', fed(produce_host_only)),
+                ('raw_beside_copy_and_kernels', fed(produce_device_only))]
+        for _, fn in legs:
+            fn(3)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        raw_fed(20)
+        steps = max(int(a.window * 20 / (time.perf_counter() - t0)), 20)          # each leg of each round lasts about --window
+        rates = {k: [] for k, _ in legs}
+        for _ in range(a.rounds):              # alternate the legs in one run
+            for key, fn in legs:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn(steps)
+                torch.cuda.synchronize()
+                rates[key].append(round(a.bs * steps / (time.perf_counter() - t0), 1))
+        res['detect'] = dict(target_size=dec.target_size, steps_per_leg=steps, images_per_s=rates)
+        producer.shutdown()
+
+    # the host baseline
+    try:
+        from PIL import Image
+    except ImportError:
+        res['pillow_ms_per_image'] = None
+    else:
+        def pil(b):
+            return np.asarray(Image.open(io.BytesIO(b)).convert('RGB'))
+        res['pillow_ms_per_image'] = {}
+        for th in (1, 16):
+            pool = ThreadPoolExecutor(th)
+            many = data * 4
+            res['pillow_ms_per_image'][str(th)] = wall_s(lambda: list(pool.map(pil, many)), a.window) * 1e3 / len(many)
+            pool.shutdown()
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
