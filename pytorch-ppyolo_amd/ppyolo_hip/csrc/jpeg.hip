@@ -1,6 +1,9 @@
-// Baseline JPEG decoding, bit for bit with libjpeg-turbo's defaults (what cv2.imread / cv2.imdecode(buf, 1) run; reference
-// demo.py:41, tools/cocotools.py:105, tools/transform.py:87): JDCT_ISLOW inverse DCT, fancy chroma upsampling, integer YCbCr
-// tables, EXIF orientation.  DESIGN.md section 10 is the numerics contract; tests/jpeg_ref.py restates it in numpy.
+// Baseline JPEG decoding with libjpeg-turbo's defaults (what cv2.imread / cv2.imdecode(buf, 1) run; reference demo.py:41,
+// tools/cocotools.py:105, tools/transform.py:87): JDCT_ISLOW inverse DCT, fancy chroma upsampling, integer YCbCr tables, EXIF
+// orientation.  Bit for bit with it wherever a block's inverse DCT stays in [-512, 511] before the range-limit table, which
+// every encoder's output does.  Beyond that range this follows libjpeg's C code (the table wraps) where libjpeg-turbo's SIMD
+// code saturates, and where an int32 intermediate overflows it wraps at 32 bits where libjpeg's JLONG has 64.  DESIGN.md
+// section 10 is the numerics contract with the three zones; tests/jpeg_ref.py restates it in numpy.
 //
 // Host part (plain C++, no GPU call, no global state => one call per image on any thread): marker parsing and Huffman
 // decoding into int16 coefficient blocks.  Device part: two launches per BATCH, whatever the number and sizes of the images --
@@ -409,7 +412,8 @@ __device__ __forceinline__ void idct_pass(const u32 in[8], u32 out[8]) {
     out[4] = tmp13 - a0;
 }
 __device__ __forceinline__ u32 descale(u32 v, int n) { return (u32)((int)(v + (1u << (n - 1))) >> n); }
-// libjpeg's range-limit table (centred on 128, indexed & 1023) in closed form: it wraps, it does not clamp.
+// libjpeg's range-limit table (centred on 128, indexed & 1023) in closed form: it wraps, it does not clamp.  Inside
+// [-512, 511] that IS a clamp; outside, libjpeg-turbo's SIMD inverse DCT saturates instead (zone B).
 __device__ __forceinline__ u32 range_limit(u32 v) {
     const u32 x = v & 1023u;
     return x < 128u ? x + 128u : x < 512u ? 255u : x < 896u ? 0u : x - 896u;

@@ -1,5 +1,6 @@
 """JPEG files -> uint8 HWC BGR device tensors, the pixels cv2.imread / cv2.imdecode(buf, 1) give (reference demo.py:41,
-tools/cocotools.py:105, tools/transform.py:87), bit for bit with libjpeg-turbo's defaults.
+tools/cocotools.py:105, tools/transform.py:87), bit for bit with libjpeg-turbo's defaults wherever a block's inverse DCT
+stays in [-512, 511], as every encoder's output does; beyond it, libjpeg's C arithmetic.
 
 Host: marker parsing + Huffman decoding into coefficient blocks, plain C++ in the library (csrc/jpeg.hip), one call per image
 on a thread pool -- ctypes releases the GIL.  Device: everything per pixel, two launches per batch (ops are in the library,

@@ -1,9 +1,14 @@
 """Numpy-only restatement of the baseline JPEG decoder of ppyolo_hip (csrc/jpeg.hip), i.e. of libjpeg-turbo with its default
 settings: JDCT_ISLOW inverse DCT (jidctint.c), fancy upsampling (jdsample.c), integer YCbCr tables (jdcolor.c), and the EXIF
-orientation as cv2.imread applies it.  decode(bytes) -> uint8 [h,w,3] BGR.  Written for reading, not for speed; the test
-files compare it with Pillow (libjpeg-turbo) where Pillow exists and with the library everywhere.
+orientation as cv2.imread applies it.  decode(bytes) -> uint8 [h,w,3] BGR = reconstruct(coefficients(bytes)): the
+coefficient dict is the seam between the host stage and the device stage of the library, and the tests drive either side of
+it.  Written for reading, not for speed; the test files compare it with Pillow (libjpeg-turbo) where Pillow exists and with
+the library everywhere.
 
-All inverse-DCT arithmetic is int32 with wrap-around, as in the kernel (no valid file comes near the range)."""
+All inverse-DCT arithmetic is int32 with wrap-around, as in the kernel, and the result goes through libjpeg's C range-limit
+table.  That equals every libjpeg-turbo build while a block's inverse DCT stays in [-512, 511] before the table (all encoder
+output does); beyond it libjpeg-turbo's SIMD code saturates where the C table wraps, and once an int32 intermediate
+overflows libjpeg's 64-bit JLONG differs too (tests/test_jpeg_synth.py)."""
 import struct
 
 import numpy as np
@@ -148,8 +153,18 @@ def parse(b):
             return dict(W=sof['W'], H=sof['H'], comps=comps, q=q, ht=ht, dri=dri, orientation=orient or 1, data=i)
 
 
+_LUTS = {}
+
+
 def _lut(spec):
     """16-bit peek -> (code length, symbol); length 0 = no such code."""
+    key = (tuple(spec[0]), tuple(spec[1]))
+    if key not in _LUTS:
+        _LUTS[key] = _build_lut(spec)
+    return _LUTS[key]
+
+
+def _build_lut(spec):
     cnt, syms = spec
     ln_ = np.zeros(65536, np.int64)
     sy_ = np.zeros(65536, np.int64)
@@ -281,38 +296,45 @@ def coefficients(b):
     return hd
 
 
-def idct(c):
-    """jidctint.c jpeg_idct_islow on dequantised int32 blocks [..., 8, 8] -> samples 0..255."""
-    c = c.astype(np.int32)
+def idct(c, prelimit=False, wide=False):
+    """jidctint.c jpeg_idct_islow on dequantised blocks [..., 8, 8] -> samples 0..255, or with prelimit=True the values that
+    index the range-limit table (the sample less 128).  wide=True evaluates in int64, where nothing can overflow (libjpeg's
+    JLONG on a 64-bit host), instead of int32 with wrap-around."""
+    np_int = np.int64 if wide else np.int32
+    c = c.astype(np_int)
 
     def p(i0, i1, i2, i3, i4, i5, i6, i7, sh):
-        z1 = (i2 + i6) * np.int32(4433)
-        t2 = z1 + i6 * np.int32(-15137)
-        t3 = z1 + i2 * np.int32(6270)
+        z1 = (i2 + i6) * np_int(4433)
+        t2 = z1 + i6 * np_int(-15137)
+        t3 = z1 + i2 * np_int(6270)
         t0 = (i0 + i4) << 13
         t1 = (i0 - i4) << 13
         t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
         a0, a1, a2, a3 = i7, i5, i3, i1
         z1, z2, z3, z4 = a0 + a3, a1 + a2, a0 + a2, a1 + a3
-        z5 = (z3 + z4) * np.int32(9633)
-        a0, a1, a2, a3 = a0 * np.int32(2446), a1 * np.int32(16819), a2 * np.int32(25172), a3 * np.int32(12299)
-        z1, z2 = z1 * np.int32(-7373), z2 * np.int32(-20995)
-        z3, z4 = z3 * np.int32(-16069) + z5, z4 * np.int32(-3196) + z5
+        z5 = (z3 + z4) * np_int(9633)
+        a0, a1, a2, a3 = a0 * np_int(2446), a1 * np_int(16819), a2 * np_int(25172), a3 * np_int(12299)
+        z1, z2 = z1 * np_int(-7373), z2 * np_int(-20995)
+        z3, z4 = z3 * np_int(-16069) + z5, z4 * np_int(-3196) + z5
         a0, a1, a2, a3 = a0 + z1 + z3, a1 + z2 + z4, a2 + z2 + z3, a3 + z1 + z4
-        r = np.int32(1 << (sh - 1))
+        r = np_int(1 << (sh - 1))
         return [(v + r) >> sh for v in (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3)]
 
     with np.errstate(over='ignore'):
         ws = np.stack(p(*[c[..., r, :] for r in range(8)], 11), axis=-2)            # pass 1: columns
         out = np.stack(p(*[ws[..., :, k] for k in range(8)], 18), axis=-1)          # pass 2: rows
+    if prelimit:
+        return out
     # the range-limit TABLE of jdmaster.c, centred on 128 and indexed & 1023: it wraps, it does not clamp
     tab = np.concatenate([np.arange(128, 256), np.full(384, 255), np.zeros(384, int), np.arange(0, 128)])
     return tab[out & 1023]
 
 
-def plane(c, q):
-    co = (c['coef'].astype(np.int32) * q[c['tq']]).reshape(c['coef'].shape[0], c['coef'].shape[1], 8, 8)
-    px = idct(co)
+def plane(c, q, prelimit=False, wide=False):
+    """One component as a block-padded plane [block rows * 8, block columns * 8]; prelimit / wide as in idct."""
+    np_int = np.int64 if wide else np.int32
+    co = (c['coef'].astype(np_int) * q[c['tq']].astype(np_int)).reshape(c['coef'].shape[0], c['coef'].shape[1], 8, 8)
+    px = idct(co, prelimit, wide)
     return px.transpose(0, 2, 1, 3).reshape(px.shape[0] * 8, px.shape[1] * 8)
 
 
@@ -365,9 +387,11 @@ def orient(a, o):
     return np.ascontiguousarray(a)
 
 
-def decode(b, apply_orientation=True):
-    hd = coefficients(b)
-    H, W, hm, vm = hd['H'], hd['W'], hd['hmax'], hd['vmax']
+def reconstruct(hd, apply_orientation=True):
+    """The device stage: coefficients -> pixels.  hd as coefficients() returns it; only W, H, orientation, q and the
+    components' h, v, tq, coef are read."""
+    H, W = hd['H'], hd['W']
+    hm, vm = max(c['h'] for c in hd['comps']), max(c['v'] for c in hd['comps'])
     pl = []
     for c in hd['comps']:
         p = plane(c, hd['q'])
@@ -395,3 +419,7 @@ def decode(b, apply_orientation=True):
         bl = np.clip(y + cbb[cb], 0, 255)
         out = np.stack([bl, g, r], -1).astype(np.uint8)
     return orient(out, hd['orientation']) if apply_orientation else out
+
+
+def decode(b, apply_orientation=True):
+    return reconstruct(coefficients(b), apply_orientation)
