@@ -14,13 +14,16 @@ a CPU-only box by interpreting the same plan with reference ops (tests/plan_inte
 the product executor below has no CPU path.
 """
 import collections
+import contextlib
 import json
 import os
 
 import torch
 
 from . import ops as K
+from . import plan_links as L
 from ._lib import PPYoloHipError
+from .plan_links import has_f16, op_io, tune_key          # noqa: F401  (tune_key: part of this module's surface)
 
 A = collections.namedtuple('A', 'buf coff C N H W')   # activation: channel slice of a buffer
 
@@ -61,22 +64,6 @@ def math_mode():
     if m not in _TUNED_PATHS:
         raise PPYoloHipError('PPYOLO_HIP_MATH must be one of %s' % sorted(_TUNED_PATHS))
     return m
-
-
-def tune_key(op, with_g=True):
-    """Shape key of a conv / DCN launch in the measured (tile config, split-K) table.  Launches that can use the
-    f16x2 kernels (split fp16 weights at hand, tracked input maximum) carry ':f' -- the same shape without them
-    (CoordConv layers, stem side) needs its own entry."""
-    x = op['x']
-    Kout, R, S, C = op['w'].shape
-    f16 = op.get('wf16') is not None and op.get('amax_in_id') is not None
-    # ('dcnf': ids of the fused DCNv2 kernel, ops.dcnv2_num_configs -- not the convolution's numbering)
-    # ':p': the layer also owns the 2x2 average of its output (HipExecutor._link_pools)
-    # ':g': the layer's input can arrive pre-split from its one producer (HipExecutor._mark_split_candidates): its main loop has
-    # no split work, another tile may win -- such entries are measured in that form; without one the plain entry is used
-    return '%s:N%d:H%d:W%d:C%d:K%d:R%d:s%d%s%s%s' % ('dcnf' if op['op'] == 'dcn' else op['op'], x.N, x.H, x.W, C, Kout, R,
-                                                     op['stride'], ':f' if f16 else '', ':p' if op.get('pool') is not None else '',
-                                                     ':g' if (op.get('gp_in') and with_g) else '')
 
 
 def tuned_table(mode=None):
@@ -263,176 +250,6 @@ class Builder(object):
         return y
 
 
-def assign_amax(ops):
-    """Blocks of tracked per-image maxima (HipExecutor._assign_amax): sets op['amax_out_id'] / ['amax_in_id'] / ['amax_in2_id'],
-    returns the number of blocks.  A conv / DCN launch merges max|y| into the block of its output BUFFER (the writers of a concat
-    buffer share one); a pooled tensor inherits the block of its input.  Round 6: when a convolution writes into a buffer that so
-    far only holds a pooled tensor -- the folded projection shortcut's wide buffer [conv2 output | pooled block input] -- the
-    buffer gets a block of its OWN for what convolutions write and keeps the inherited one as a second, read-only block
-    ('amax_in2_id' of its readers): the block input's other readers (the head's C3 / C4 convolutions) no longer see conv2's
-    maximum (round-5 advisor)."""
-    amax_of, aux_of, inherited, nblocks = {}, {}, set(), 0
-    for op in ops:
-        t = op['op']
-        if t in ('conv', 'dcn'):
-            b = op['y'].buf
-            if b in inherited:
-                inherited.discard(b)
-                aux_of[b] = amax_of.pop(b)
-            if b not in amax_of:
-                amax_of[b] = nblocks
-                nblocks += 1
-            op['amax_out_id'] = amax_of[b]
-            op['amax_in_id'] = amax_of.get(op['x'].buf)
-            op['amax_in2_id'] = aux_of.get(op['x'].buf)
-        elif t in ('maxpool', 'avgpool'):
-            src = amax_of.get(op['x'].buf)
-            if src is not None:
-                yb = op['y'].buf
-                if yb in amax_of and yb not in inherited:      # a convolution wrote into this buffer first: second block
-                    aux_of[yb] = src
-                else:
-                    amax_of[yb] = src
-                    inherited.add(yb)
-        elif t == 'stem':
-            amax_of[op['y'].buf] = nblocks
-            op['amax_out_id'] = nblocks
-            nblocks += 1
-    return nblocks
-
-
-def link_pools(ops, op_io, has_f16, two_streams=False):
-    """Host logic of HipExecutor._link_pools, device-free (tests/test_plan_host_logic.py): gives every 'avgpool' op whose input
-    slice is written by exactly one 1x1 / stride-1 convolution that ppy_conv1x1_expand_f32 accepts (C = 64 with K % 64 == 0, or
-    C = 128 with K % 128 == 0; K / 64 resp. K / 128 a power of two <= 16; no upsampling, no position bias; has_f16(op): f16x2
-    operands at hand) to that convolution: conv['pool'] = the pooled slice, avgpool['owner'] = the convolution.  op_io(op) ->
-    (input buffer ids, output buffer ids).  Returns the number of links."""
-    n = 0
-    for i, op in enumerate(ops):
-        if op['op'] != 'avgpool':
-            continue
-        x = op['x']
-        # (a route buffer has several writers, each of its own channel slice: the producer is the one that writes x's)
-        prods = [o for o in ops[:i] if x.buf in op_io(o)[1] and (o['op'] != 'conv' or (o['y'].coff < x.coff + x.C
-                                                                                      and x.coff < o['y'].coff + o['y'].C))]
-        if len(prods) != 1 or prods[0]['op'] != 'conv':
-            continue
-        c = prods[0]
-        Kout, R, S, C = c['w'].shape
-        y = c['y']
-        groups = Kout // 64 if C == 64 else Kout // 128           # (what ppy_conv1x1_expand_f32 accepts)
-        if (R, S, c['stride']) != (1, 1, 1) or C not in (64, 128) or Kout % (64 if C == 64 else 128) or groups & (groups - 1) \
-                or groups > 16 or c['ups'] or c['posb'] is not None or not has_f16(c) \
-                or (two_streams and c.get('stream', 0) != op.get('stream', 0)) \
-                or (y.buf, y.coff, y.C) != (x.buf, x.coff, x.C) or x.H % 2 or x.W % 2 or x.H * x.W < 32:
-            continue
-        c['pool'] = op['y']
-        op['owner'] = c
-        n += 1
-    return n
-
-
-def link_maxpools(ops, op_io, pinned, has_f16):
-    """Host logic of HipExecutor._link_maxpools, device-free (tests/test_plan_host_logic.py): a 'maxpool' op (MaxPool2d(3, 2, 1), the
-    stem's) whose input is the WHOLE buffer written by one convolution that ppy_conv3x3_maxpool_f32 accepts (3x3 / stride 1 / pad 1,
-    C = 32 -> K = 64, no shortcut / upsampling / position bias; has_f16(op): f16x2 operands at hand) and read by nothing else:
-    conv['mpool'] = the pooled slice, maxpool['owner'] = the convolution, whose launch then writes ONLY the pooled tensor.
-    Returns the number of links."""
-    n = 0
-    for i, op in enumerate(ops):
-        if op['op'] != 'maxpool':
-            continue
-        x = op['x']
-        prods = [o for o in ops if x.buf in op_io(o)[1]]
-        readers = [o for o in ops if o is not op and x.buf in op_io(o)[0]]
-        if len(prods) != 1 or prods[0]['op'] != 'conv' or readers or x.buf in pinned:
-            continue
-        c = prods[0]
-        Kout, R, S, C = c['w'].shape
-        y = c['y']
-        if (R, S, c['stride'], c['pad'], C, Kout) != (3, 3, 1, 1, 32, 64) or c['ups'] or c['posb'] is not None or c['res'] is not None \
-                or c.get('pool') is not None or not has_f16(c) or c.get('stream', 0) != op.get('stream', 0) \
-                or (y.buf, y.coff, y.C) != (x.buf, x.coff, x.C) or x.coff != 0:
-            continue
-        c['mpool'] = op['y']
-        op['owner'] = c
-        n += 1
-    return n
-
-
-def split_pairs(ops, op_io, buffers, pinned, has_f16, only_3x3=False):
-    """Host logic of HipExecutor._link_splits, device-free (tests/test_plan_host_logic.py): [(producer, [consumers])] between which
-    a tensor may travel PRE-SPLIT, whatever tiles they run on -- a buffer written by ONE convolution (the whole
-    buffer, no shortcut term, no upsampled store, no pooled twin, a multiple of 32 channels) and read ONLY by convolutions, as
-    their input: a bottleneck's conv1 -> conv2, the head's 1x1 -> 3x3 -> 1x1 chains, and a route with its two readers (the tip
-    3x3 and the 1x1 in front of the upsampling).  pinned: buffers that something outside the convolution chain reads (feature
-    maps, head outputs).  has_f16(op): f16x2 operands at hand.  only_3x3: A/B switch -- 1x1 consumers gain less (they split every
-    activation once per wave column, a 3x3 nine times) but they gain: R50vd-608 bs 8 +0.9 % on top of the 3x3 links."""
-    readers, writers = {}, {}
-    for op in ops:
-        ins, outs = op_io(op)
-        for b in ins:
-            readers.setdefault(b, []).append(op)
-        for b in outs:
-            writers.setdefault(b, []).append(op)
-    pairs = []
-    for b, ws_ in writers.items():
-        if len(ws_) != 1 or b in pinned:
-            continue
-        pr = ws_[0]
-        ld = buffers[b][3]
-        y = pr.get('y')
-        if pr['op'] != 'conv' or not has_f16(pr) or pr['ups'] or pr['res'] is not None or pr.get('pool') is not None \
-                or y.buf != b or y.coff != 0 or y.C != ld or ld % 32:
-            continue
-        cons = readers.get(b, [])
-        ok = bool(cons)
-        for c in cons:
-            x = c.get('x')
-            if c['op'] != 'conv' or not has_f16(c) or x is None or x.buf != b or x.coff != 0 or x.C != ld \
-                    or (c['res'] is not None and c['res'].buf == b) or (only_3x3 and c['w'].shape[1] != 3):
-                ok = False
-        if ok and len(set(id(c) for c in cons)) == len(cons):
-            pairs.append((pr, cons))
-    return pairs
-
-
-def b2b_pairs(ops, op_io, buffers, pinned, has_f16):
-    """Host logic of HipExecutor._mark_b2b, device-free: [(conv A, conv B)] that ppy_conv3x3_conv1x1_f32 can run as ONE launch --
-    conv2 -> conv3 of an identity bottleneck (reference model/resnet_vd.py:81-87): A = 3x3 / stride 1 / pad 1, 64 -> 64, ReLU, no
-    shortcut / position bias / upsampling, writing a whole buffer that ONLY B reads; B = 1x1 / stride 1, 64 -> 256, ReLU, with a
-    shortcut, no position bias / upsampling."""
-    readers, writers = {}, {}
-    for op in ops:
-        ins, outs = op_io(op)
-        for b in ins:
-            readers.setdefault(b, []).append(op)
-        for b in outs:
-            writers.setdefault(b, []).append(op)
-    out = []
-    for a in ops:
-        if a['op'] != 'conv' or not has_f16(a):
-            continue
-        Ka, R, S, Ca = a['w'].shape
-        y = a['y']
-        if (R, S, a['stride'], a['pad'], Ca, Ka, a['act']) != (3, 3, 1, 1, 64, 64, 'relu') or a['res'] is not None or a['posb'] is not None \
-                or a['ups'] or a.get('pool') is not None or a.get('mpool') is not None or y.buf in pinned \
-                or y.coff != 0 or y.C != buffers[y.buf][3] or len(writers.get(y.buf, [])) != 1:
-            continue
-        rd = readers.get(y.buf, [])
-        if len(rd) != 1 or rd[0]['op'] != 'conv':
-            continue
-        b = rd[0]
-        Kb, Rb, Sb, Cb = b['w'].shape
-        x = b['x']
-        if (Rb, Sb, b['stride'], b['pad'], Cb, Kb, b['act']) != (1, 1, 1, 0, 64, 256, 'relu') or b['res'] is None or b['posb'] is not None \
-                or b['ups'] or not has_f16(b) or (x.buf, x.coff, x.C) != (y.buf, 0, 64) or b['res'].buf == y.buf \
-                or b.get('stream', 0) != a.get('stream', 0):
-            continue
-        out.append((a, b))
-    return out
-
-
 # =========================================================================================
 class HipExecutor(object):
     """Binds a Plan to device buffers and replays it through libppyolo_hip.so."""
@@ -490,23 +307,23 @@ class HipExecutor(object):
                             op['w3'] = K.split_weights_bf16x3(op['w'])
                             if self.math == 'f16x2':
                                 op['wf16'] = K.split_weights_f16x2(op['w'], op['scale'])
-        self._assign_amax()
-        self._want_streams = os.environ.get('PPYOLO_HIP_STREAMS', '1') == '2' if multi_stream is None else bool(multi_stream)
-        self._link_pools()
-        self._link_maxpools()
+        # The link state is derived in ONE order (plan_links.py).  1: the tracked per-image tensor maxima
+        self._amax_block = p.N * K.AMAX_FLOATS_PER_IMAGE
+        self.amax = torch.zeros(max(1, L.assign_amax(p.ops)) * self._amax_block, dtype=torch.float32, device=self.device)
+        # 2: the structural links -- the vd shortcut's average pool, then the stem's max pool, go to the launch in front of them
+        f16x2, env = self.math == 'f16x2', os.environ.get
+        self._want_streams = env('PPYOLO_HIP_STREAMS', '1') == '2' if multi_stream is None else bool(multi_stream)
+        self._pinned = {a.buf for a in list(p.head_outs) + list(p.feats)}      # read from outside the convolution chain
+        if f16x2 and env('PPYOLO_HIP_POOL_FOLD', '1') == '1':
+            L.link_pools(L.BufferIndex(p.ops), has_f16, self._want_streams)
+        if f16x2 and env('PPYOLO_HIP_MAXPOOL_FOLD', '1') == '1':          # (=0: two launches)
+            L.link_maxpools(L.BufferIndex(p.ops), self._pinned, has_f16)
+        self._index = L.BufferIndex(p.ops)          # (final: a fused pair is a decision of _link_splits, not a structural link)
+        # 3: the buffers; 4: the layers whose input can arrive pre-split ('gp_in' is part of the table key), then the measured table
         self._alloc_buffers()
-        tab = tuned_table(self.math)
-        tab_x3 = tuned_table('bf16x3') if self.math == 'f16x2' else {}
         self._mark_split_candidates()
-        for op in p.ops:
-            if op['op'] in ('conv', 'dcn') and op['cfg'] < 0:
-                ent = tab.get(tune_key(op)) or tab.get(tune_key(op, False)) or tab_x3.get(tune_key(op, False))      # (a layer without ':f' behaves as in bf16x3 mode)
-                if not ent and op.get('pool') is not None:                   # no entry for the pooled form: the plain shape's
-                    k0 = tune_key(dict(op, pool=None), False)
-                    ent = tab.get(k0) or tab_x3.get(k0)
-                if ent:
-                    op['cfg'], op['splitk'] = ent[:2]
-        if os.environ.get('PPYOLO_HIP_HEAD_TAIL_FP32', '0') == '1':
+        L.apply_tuned(p.ops, tuned_table(self.math), tuned_table('bf16x3') if f16x2 else {})
+        if env('PPYOLO_HIP_HEAD_TAIL_FP32', '0') == '1':
             # experiment (round-5 review, item 7): the last two convolutions of every head level -- the tip 3x3 and the output 1x1 -- on
             # the exact-fp32 MFMA kernels, everything in front of them as usual.  Measured: does not move the count of boxes beyond
             # 1e-3 px at R50vd-608; off by default.
@@ -517,18 +334,15 @@ class HipExecutor(object):
                 x = op['x']
                 Kout, R, S, C = op['w'].shape
                 op['cfg'], op['splitk'] = K.conv2d_pick(x.N, x.H, x.W, C, Kout, R, S, op['stride'], op['pad'])
-        self.ws = None
-        self.ws_side = None
+        self.ws = self.ws_side = None
         self._size_workspace()
         # Independent branches (projection shortcut, head tip / output convs) on a second stream: OPT-IN
         # (PPYOLO_HIP_STREAMS=2).  A forked graph gains 3 % for one batch at a time (R50-608 bs8 1481 -> 1526 img/s; small
         # batches lose on the fork/join), but keeping two batches in flight on two single-branch graphs (runtime.InFlight)
         # gains 24 % where two forked ones gain 3 %, and a forked hipGraph replayed under another stream than its first
         # has crashed the ROCm 7.2 runtime -- so the default is one branch, and a forked graph refuses a stream change.
-        want = self._want_streams
-        self.multi_stream = want and any(op.get('stream', 0) for op in p.ops)
+        self.multi_stream = self._want_streams and any(op.get('stream', 0) for op in p.ops)
         self.side_stream = torch.cuda.Stream(device=self.device) if self.multi_stream else None
-        self._build_sync_plan()
         with torch.cuda.device(self.device):
             for op in p.setup_ops:
                 self._run_op(op)
@@ -546,7 +360,7 @@ class HipExecutor(object):
         p = self.plan
         used = set(p.consts)
         for op in p.setup_ops + p.ops:
-            ins, outs = self._op_io(op)
+            ins, outs = op_io(op)
             used.update(ins)
             used.update(outs)
             if op.get('posb') is not None:
@@ -564,134 +378,74 @@ class HipExecutor(object):
             else:
                 self.bufs.append(None)
 
-    def _assign_amax(self):
-        """Tracked per-image tensor maxima for the f16x2 kernels: every conv / DCN launch merges max|y| into the slots of its
-        output buffer; pooled tensors inherit the slots of their input (max- and average-pooling never exceed it; SPP
-        writes into its own input buffer; the DCN columns are bounded by the DCN input); the stem kernel tracks its
-        output as well."""
-        nblocks = assign_amax(self.plan.ops)
-        self._amax_block = self.plan.N * K.AMAX_FLOATS_PER_IMAGE
-        self.amax = torch.zeros(max(1, nblocks) * self._amax_block, dtype=torch.float32, device=self.device)
-
-    def _link_pools(self):
-        """The vd shortcut's AvgPool2d(2, 2) (reference model/resnet_vd.py:29-33) belongs to the launch that produces its
-        input where that is a 1x1 convolution the streaming kernel (csrc/conv_stream.hip) can run: the producer then
-        writes the 2x2 average from its own epilogue (cfg = a streaming id) or, on any other tile, the pooling launch
-        follows it immediately; the 'avgpool' op of the plan is skipped either way."""
-        if self.math != 'f16x2' or os.environ.get('PPYOLO_HIP_POOL_FOLD', '1') != '1':
-            return
-        link_pools(self.plan.ops, self._op_io, lambda c: c.get('wf16') is not None and c.get('amax_in_id') is not None,
-                   self._want_streams)
-
-    def _link_maxpools(self):
-        """The stem's MaxPool2d(3, 2, 1) (reference model/resnet_vd.py:103, 136) belongs to the launch of the convolution in front of
-        it (csrc/conv_patch.hip, MPOOL): the 304 x 304 x 64 tensor between them is neither written nor read.
-        PPYOLO_HIP_MAXPOOL_FOLD=0: two launches."""
-        if self.math != 'f16x2' or os.environ.get('PPYOLO_HIP_MAXPOOL_FOLD', '1') != '1':
-            return
-        pinned = {a.buf for a in list(self.plan.head_outs) + list(self.plan.feats)}
-        link_maxpools(self.plan.ops, self._op_io, pinned, lambda c: c.get('wf16') is not None and c.get('amax_in_id') is not None)
-
     @staticmethod
     def split_capable(cfg, consumer):
         """Does this tile configuration read (consumer) / write pre-split tensors?"""
-        return cfg >= 0 and (K.conv_cfg(cfg).reads_presplit if consumer else K.conv_cfg(cfg).writes_presplit)
+        return L.split_capable(cfg, consumer, K.conv_cfg)
 
-    @staticmethod
-    def _split_leaves_launch(op):
-        """Does this op's split-K go through partial sums in memory (a second launch combines them)?  Such a launch neither reads nor
-        writes pre-split tensors."""
-        return op.get('splitk', 0) > 1 and not (op['op'] == 'conv' and op.get('cfg', -1) >= 0 and K.conv_cfg(op['cfg']).splitk_mode == 'workgroup')
-
-    def _split_pairs(self):
-        """[(producer, [consumers])] that qualify STRUCTURALLY for a pre-split tensor between them (split_pairs below)."""
-        if self.math != 'f16x2' or os.environ.get('PPYOLO_HIP_PRESPLIT', '1') != '1':
-            return []
-        pinned = {a.buf for a in list(self.plan.head_outs) + list(self.plan.feats)}      # read from outside the conv chain
-        return split_pairs(self.plan.ops, self._op_io, self.plan.buffers, pinned,
-                           lambda c: c.get('wf16') is not None and c.get('amax_in_id') is not None,
-                           os.environ.get('PPYOLO_HIP_PRESPLIT_3X3_ONLY', '0') == '1')
+    def _switches(self):
+        """The A/B switches of the cfg-dependent links, read at every derivation (PPYOLO_HIP_B2B=0: conv2 -> conv3 as two launches)."""
+        f16x2, env = self.math == 'f16x2', os.environ.get
+        return dict(presplit=f16x2 and env('PPYOLO_HIP_PRESPLIT', '1') == '1', only_3x3=env('PPYOLO_HIP_PRESPLIT_3X3_ONLY', '0') == '1',
+                    b2b=f16x2 and env('PPYOLO_HIP_B2B', '1') == '1')
 
     def _mark_split_candidates(self):
+        """op['gp_in']: the op's input qualifies STRUCTURALLY for arriving pre-split (plan_links.split_pairs), whatever the tiles."""
         for op in self.plan.ops:
             op.pop('gp_in', None)
-        for _, cons in self._split_pairs():
-            for c in cons:
-                c['gp_in'] = True
+        sw = self._switches()
+        if sw['presplit']:
+            for _, cons in L.split_pairs(self._index, self.plan.buffers, self._pinned, has_f16, sw['only_3x3']):
+                for c in cons:
+                    c['gp_in'] = True
 
     def _unlink_splits(self):
+        """Every op a launch of its own on plain fp32 tensors (what is left: the structural links of the pools)."""
         for op in self.plan.ops:
-            op.pop('x_split', None)
-            op.pop('y_split', None)
+            for k in ('x_split', 'y_split', 'b2b', 'b2b_of'):
+                op.pop(k, None)
 
-    def _link_splits(self, _retry=False):
-        """"Global pre-split" (DESIGN.md 4.1g): where a convolution's output buffer is read by exactly ONE op, a convolution on
-        an f16x2 tile kernel, the producer stores it as that consumer's finished MFMA operands (two fp16 terms of y * s_image,
-        same bytes per pixel) and the consumer's main loop carries no scale / split work.  s_image comes from a static bound
-        of |y| -- per output channel |scale| * sum|w| times the input's tracked maximum, plus |shift| and the CoordConv bias --
-        so the producer needs no second pass.  Bottleneck conv1 -> conv2 (3x3) and the head's 1x1 -> 3x3 pairs qualify."""
-        if not _retry:
-            self._b2b_rejected = set()      # (op indices of fused pairs that fell back to two launches in this derivation)
+    def _link_splits(self):
+        """The cfg-dependent links, from scratch (call it, with _size_workspace, after changing a tile id): which pre-split links and
+        fused conv2 -> conv3 pairs the tiles of op['cfg'] / ['splitk'] allow (plan_links.decide_links), their tensors and bounds,
+        and the cross-stream waits of the plan as it then launches.  Returns the number of consumers linked.  A link's per-image
+        scale s_image is ONE tensor (the producer's y_split[0], every consumer's x_split); it derives from the static bound in y_split[1:]."""
+        ops = self.plan.ops
         self._unlink_splits()
-        self._mark_b2b()
-        n = 0
-        for pr, cons in self._split_pairs():
-            if pr.get('b2b') is not None or pr.get('b2b_of') is not None:
-                continue          # (the fused pair's output is plain fp32: it is a shortcut as well)
-            if self._split_leaves_launch(pr) or not self.split_capable(pr['cfg'], False) \
-                    or any(c.get('b2b') is None and (self._split_leaves_launch(c) or not self.split_capable(c['cfg'], True)) for c in cons):
-                continue          # (every reader must take the tensor in that form, or none does)
-            w, sc, sh = pr['w'], pr['scale'], pr['shift']
-            l1 = w.abs().double().sum(dim=(1, 2, 3))
-            mul = float((sc.abs().double() * l1).max())
-            add = sh.abs().double()
-            if pr['posb'] is not None:
-                pb = self.bufs[pr['posb'].buf].abs().double().reshape(-1, w.shape[0]).amax(dim=0)
-                add = add + pb * sc.abs().double()
-            add = float(add.max())
+        links, fused, _ = L.decide_links(ops, self._index, self.plan.buffers, self._pinned, has_f16, K.conv_cfg, **self._switches())
+        for a, b in fused:
+            if ops[a].get('t_bound') is None:          # (bound of the tensor between the two: the first conv has no position bias)
+                ops[a]['t_bound'] = L.static_bound(ops[a])
+            ops[a]['b2b'], ops[b]['b2b_of'] = ops[b], ops[a]
+        for pr, cons in links:
+            pr = ops[pr]
+            pb = None if pr['posb'] is None else self.bufs[pr['posb'].buf].abs().double().reshape(-1, pr['w'].shape[0]).amax(dim=0)
             ps = torch.ones(self.plan.N, dtype=torch.float32, device=self.device)
-            pr['y_split'] = (ps, mul * (1.0 + 2.0 ** -8), add * (1.0 + 2.0 ** -8) + 1e-30)
+            pr['y_split'] = (ps,) + L.static_bound(pr, pb)
             for c in cons:
-                c['x_split'] = ps
-                n += 1
-        # a fused pair needs its input pre-split (csrc/conv_b2b.hip reads finished operands): without the link it is two launches again
-        undone = False
-        for i, op in enumerate(self.plan.ops):
-            if op.get('b2b') is not None and op.get('x_split') is None:
-                self._b2b_rejected.add(i)
-                undone = True
-        if undone:      # (the links were derived with that pair fused: its stand-alone form may allow others; the other pairs stay fused)
-            return self._link_splits(_retry=True)
-        return n
+                ops[c]['x_split'] = ps
+        self._waits, self._needs_event, self._side_tail = L.sync_plan(ops, self.multi_stream)
+        return sum(len(cons) for _, cons in links)
 
-    def _unlink_b2b(self):
-        for op in self.plan.ops:
-            if op.get('b2b') is not None:
-                op['b2b'].pop('b2b_of', None)
-                op.pop('b2b', None)
+    def _measure_form(self, op, scales):
+        """A layer is measured as it will run: with a pre-split input where it can arrive so ('gp_in') and the tile and split-K now in
+        op['cfg'] / ['splitk'] take it (`scales`: any per-image scale tensor -- the timing does not depend on the values read)."""
+        op.pop('x_split', None)
+        if op.get('gp_in') and L.takes_presplit(op, K.conv_cfg):
+            op['x_split'] = scales
 
-    def _mark_b2b(self):
-        """conv2 -> conv3 of an identity bottleneck as ONE launch (round 5, csrc/conv_b2b.hip; PPYOLO_HIP_B2B=0: two launches): the
-        64-channel tensor between them is neither written nor read.  The static bound of the intermediate (per-image operand scale
-        of the second contraction) is derived as for a pre-split link."""
-        self._unlink_b2b()
-        if self.math != 'f16x2' or os.environ.get('PPYOLO_HIP_B2B', '1') != '1':
-            return 0
-        pinned = {a.buf for a in list(self.plan.head_outs) + list(self.plan.feats)}
-        pairs = b2b_pairs(self.plan.ops, self._op_io, self.plan.buffers, pinned,
-                          lambda c: c.get('wf16') is not None and c.get('amax_in_id') is not None)
-        # pairs that did not get their pre-split input in an earlier pass of _link_splits stay two launches (round-5 advisor: only
-        # those, not every pair of the plan); the set is cleared whenever the links are rebuilt from scratch (a new tile table)
-        rejected = {id(self.plan.ops[i]) for i in getattr(self, '_b2b_rejected', ())}
-        pairs = [(a, b) for a, b in pairs if id(a) not in rejected]
-        for a, b in pairs:
-            if a.get('t_bound') is None:
-                w, sc, sh = a['w'], a['scale'], a['shift']
-                l1 = w.abs().double().sum(dim=(1, 2, 3))
-                a['t_bound'] = (float((sc.abs().double() * l1).max()) * (1.0 + 2.0 ** -8), float(sh.abs().double().max()) * (1.0 + 2.0 ** -8) + 1e-30)
-            a['b2b'] = b
-            b['b2b_of'] = a
-        return len(pairs)
+    @contextlib.contextmanager
+    def _tuning(self):
+        """Around a tuner: layers are measured unlinked, on plain fp32 tensors; the links are re-derived from the new choices."""
+        self._unlink_splits()
+        yield
+        self._size_workspace()
+        self._link_splits()
+        self.graph = None
+
+    def _commit(self, op, cfg, splitk, ms):
+        op['cfg'], op['splitk'] = cfg, splitk
+        tuned_table(self.math)[tune_key(op)] = [cfg, splitk, round(ms, 4)]
 
     def presplit_headroom(self):
         """Diagnostic (host sync; after a run): for every pre-split link and image, (key of the producer, log2 of the SCALED
@@ -745,55 +499,6 @@ class HipExecutor(object):
         if self.ws_side is None or self.ws_side.numel() * 4 < need_side:      # concurrent branch: own scratch
             self.ws_side = torch.empty(((need_side + 3) // 4,), dtype=torch.float32, device=self.device)
 
-    @staticmethod
-    def _op_io(op):
-        """(input buffer ids, output buffer ids) of a plan op."""
-        t = op['op']
-        if t == 'conv' and op.get('b2b_of') is not None:         # computed inside the launch of the convolution in front of it (_mark_b2b)
-            return [], []
-        if t == 'conv' and op.get('b2b') is not None:
-            b = op['b2b']
-            return [op['x'].buf, b['res'].buf], [b['y'].buf] + ([b['pool'].buf] if b.get('pool') is not None else [])
-        if t == 'conv':
-            ins = [op['x'].buf] + ([op['res'].buf] if op['res'] is not None else [])
-            if op.get('mpool') is not None:          # only the pooled tensor is written (_link_maxpools)
-                return ins, [op['mpool'].buf]
-            return ins, [op['y'].buf] + ([op['pool'].buf] if op.get('pool') is not None else [])
-        if t == 'stem':
-            return [], [op['y'].buf]
-        if t in ('avgpool', 'maxpool') and op.get('owner') is not None:      # written by its producer's launch (_link_pools / _link_maxpools)
-            return [], []
-        if t in ('maxpool', 'avgpool'):
-            return [op['x'].buf], [op['y'].buf]
-        if t == 'spp':
-            return [op['x'].buf], [op['y5'].buf]
-        if t == 'dcn':
-            return [op['x'].buf, op['om'].buf], [op['y'].buf]
-        raise PPYoloHipError('unknown plan op %r' % t)
-
-    def _build_sync_plan(self):
-        """Cross-stream dependencies, derived once: an op waits for every earlier writer of a buffer
-        it reads that ran on the other stream (buffers are never reused, concat buffers have
-        several writers of disjoint slices -> wait for all of them)."""
-        ops = self.plan.ops
-        writers = {}
-        self._waits = [[] for _ in ops]          # op index -> producer op indices on the other stream
-        self._needs_event = set()
-        for i, op in enumerate(ops):
-            ins, outs = self._op_io(op)
-            s = op.get('stream', 0) if self.multi_stream else 0
-            for bid in ins:
-                for j in writers.get(bid, []):
-                    sj = ops[j].get('stream', 0) if self.multi_stream else 0
-                    if sj != s and j not in self._waits[i]:
-                        self._waits[i].append(j)
-                        self._needs_event.add(j)
-            for bid in outs:
-                writers.setdefault(bid, []).append(i)
-        # tail of the side stream must be joined before decode / the end of the step
-        self._side_tail = max([i for i, op in enumerate(ops) if op.get('stream', 0)], default=None) \
-            if self.multi_stream else None
-
     def _run_op(self, op, ws=None):
         t = op['op']
         ws = self.ws if ws is None else ws
@@ -831,10 +536,10 @@ class HipExecutor(object):
                         self._amax(op.get('amax_out_id')),
                         mfma=self.math != 'fp32' and op['w'].shape[0] == 32 and os.environ.get('PPYOLO_HIP_STEM_MFMA', '1') == '1')
         elif t == 'maxpool':
-            if op.get('owner') is None:          # (else: written by the producer's launch, _link_maxpools)
+            if op.get('owner') is None:          # (else: written by the producer's launch, link_maxpools)
                 K.maxpool3x3s2(self.view(op['x']), self.view(op['y']))
         elif t == 'avgpool':
-            if op.get('owner') is None:          # (else: written by the producer's launch, _link_pools)
+            if op.get('owner') is None:          # (else: written by the producer's launch, link_pools)
                 K.avgpool2x2(self.view(op['x']), self.view(op['y']))
         elif t == 'spp':
             K.spp(self.view(op['x']), self.view(op['y5']), self.view(op['y9']), self.view(op['y13']))
@@ -926,9 +631,7 @@ class HipExecutor(object):
         cfgs_dcn = K.dcnv2_configs(self.math)      # schemes up to this mode's (+ the eight-wave f16x2 tiles)
         splits = (1, 2, 3, 4, 6, 8, 9, 12, 16)
         report = []
-        self._unlink_splits()          # (layers are measured on plain fp32 tensors; the links are re-derived from the new choices)
-        self._unlink_b2b()
-        with torch.cuda.device(self.device):
+        with self._tuning(), torch.cuda.device(self.device):
             big = 0
             for op in self.plan.ops:
                 if op['op'] in ('conv', 'dcn'):
@@ -950,11 +653,7 @@ class HipExecutor(object):
 
                 def measure(c, s, n):
                     op['cfg'], op['splitk'] = c, s
-                    # a layer whose input will arrive pre-split is measured in that form on the tiles that can read it (the
-                    # bytes it reads are whatever the buffer holds: the timing does not depend on the values)
-                    op.pop('x_split', None)
-                    if gp_scales is not None and not self._split_leaves_launch(op) and self.split_capable(c, True):
-                        op['x_split'] = gp_scales
+                    self._measure_form(op, gp_scales)
                     try:
                         self._run_op(op)
                     except PPYoloHipError:
@@ -1027,15 +726,11 @@ class HipExecutor(object):
                 if best is None:
                     op['cfg'], op['splitk'] = base_cfg, base_split
                     continue
-                op['cfg'], op['splitk'] = best[1], best[2]
-                tuned_table(self.math)[tune_key(op)] = [best[1], best[2], round(best[0], 4)]
+                self._commit(op, best[1], best[2], best[0])
                 report.append((tune_key(op), best))
                 if verbose:
                     print('autotune %s w=%s H=%d -> cfg %d split %d  %.3f ms' % (op['op'], tuple(op['w'].shape),
                                                                                op['x'].H, best[1], best[2], best[0]))
-        self._size_workspace()
-        self._link_splits()
-        self.graph = None
         return report
 
     def co_tune(self, other, topk=4, reps=3, verbose=False):
@@ -1045,9 +740,7 @@ class HipExecutor(object):
         The fastest kernel alone is not always the best neighbour: a tile shape that leaves CUs, LDS or power to the
         other lane can finish the pair sooner.  Measured, R50-608 bs8, two lanes: +0.6 %."""
         import time
-        self._unlink_splits()
-        self._unlink_b2b()
-        with torch.cuda.device(self.device):
+        with self._tuning(), torch.cuda.device(self.device):
             sa, sb = torch.cuda.Stream(device=self.device), torch.cuda.Stream(device=self.device)
             with torch.cuda.stream(sb):
                 other.run()
@@ -1092,14 +785,10 @@ class HipExecutor(object):
                 win = scored[0]
                 if (win[1], win[2]) != (front[0][1], front[0][2]):
                     changed += 1
-                op['cfg'], op['splitk'] = win[1], win[2]
-                tuned_table(self.math)[tune_key(op)] = [win[1], win[2], round(win[3], 4)]
+                self._commit(op, win[1], win[2], win[3])
                 if verbose:
                     print('co_tune %s: %s -> cfg %d split %d' % (tune_key(op), ['%d/%d %.3f' % (c, s, 1e3 * b)
                                                                               for b, c, s, _ in scored], win[1], win[2]))
-        self._size_workspace()
-        self._link_splits()
-        self.graph = None
         return changed
 
     def insitu_tune(self, topk=6, reps=5, verbose=False):
@@ -1107,10 +796,8 @@ class HipExecutor(object):
         whole eager pass of the plan (HIP events around that one launch, best of `reps` passes) -- where the layer's weights and
         activations come from wherever the rest of the step left them, not from the caches its own previous repetition warmed
         (the stage-4 1x1 layers take 29 us back to back and 39-42 us in the step)."""
-        self._unlink_splits()
-        self._unlink_b2b()
         changed = 0
-        with torch.cuda.device(self.device):
+        with self._tuning(), torch.cuda.device(self.device):
             self._size_workspace()
             ops = self.plan.ops
             for i, op in enumerate(ops):
@@ -1143,13 +830,9 @@ class HipExecutor(object):
                     win = inc[0]          # (autotune(only_cfgs=...): the table's entry stays unless a challenger is >= 3 % faster inside the step too)
                 if (win[1], win[2]) != (front[0][1], front[0][2]):
                     changed += 1
-                op['cfg'], op['splitk'] = win[1], win[2]
-                tuned_table(self.math)[tune_key(op)] = [win[1], win[2], round(win[3], 4)]
+                self._commit(op, win[1], win[2], win[3])
                 if verbose:
                     print('insitu_tune %s: %s -> cfg %d split %d' % (tune_key(op), ['%d/%d %.1f' % (c, s, 1e3 * b) for b, c, s, _ in scored], win[1], win[2]))
-        self._size_workspace()
-        self._link_splits()
-        self.graph = None
         return changed
 
     def save_tuning(self, path):

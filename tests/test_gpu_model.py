@@ -536,6 +536,43 @@ def test_b2b_pairs_in_the_plan_and_same_detections(monkeypatch):
         assert float((a[:, 1] - b[:, 1]).abs().max()) <= 1e-5 and float((a[:, 2:] - b[:, 2:]).abs().max()) <= 2e-3
 
 
+def test_links_on_the_device_are_the_device_free_derivation():
+    """HipExecutor._link_splits only attaches tensors to what plan_links decides: for the R50vd plan with stage 2 on tiles that
+    read / write pre-split tensors (the recipe of the test above), 'b2b', 'b2b_of', 'x_split' and 'y_split' sit exactly where
+    decide_links, run on a copy of the plan without them, places them; a link's scale is ONE tensor for its producer and every
+    consumer; and the cross-stream waits are sync_plan over the final state."""
+    from ppyolo_hip import ops as K
+    from ppyolo_hip import plan_links as L
+    N, S = 2, 160
+    model, _ = build_model(PPYOLO_2x_Config(), 0, 'cuda')
+    ex = model._plans.executor(synth.synth_images(N, S, seed=77).cuda())
+    ops = ex.plan.ops
+    for op in ops:
+        if op['op'] == 'conv' and op['x'].H == S // 4 and op['cfg'] < 0 and op.get('wf16') is not None and op.get('amax_in_id') is not None:
+            op['cfg'], op['splitk'] = 44, 1
+    ex._size_workspace()
+    n = ex._link_splits()
+    bare = [{k: v for k, v in op.items() if k not in ('b2b', 'b2b_of', 'x_split', 'y_split')} for op in ops]
+    pinned = {a.buf for a in list(ex.plan.head_outs) + list(ex.plan.feats)}
+    links, fused, _ = L.decide_links(bare, L.BufferIndex(bare), ex.plan.buffers, pinned, L.has_f16, K.conv_cfg)
+    assert len(fused) == 2 and n == sum(len(cons) for _, cons in links) > 0
+    want = [dict() for _ in ops]
+    for a, b in fused:
+        want[a]['b2b'], want[b]['b2b_of'] = b, a
+        bare[a]['b2b'], bare[b]['b2b_of'] = bare[b], bare[a]
+    for pr, cons in links:
+        want[pr]['y_split'] = pr
+        for c in cons:
+            want[c]['x_split'] = pr
+    for i, op in enumerate(ops):
+        assert {k for k in ('b2b', 'b2b_of', 'x_split', 'y_split') if op.get(k) is not None} == set(want[i]), i
+        for k in ('b2b', 'b2b_of'):
+            assert k not in want[i] or op[k] is ops[want[i][k]], (i, k)
+        assert 'x_split' not in want[i] or op['x_split'] is ops[want[i]['x_split']]['y_split'][0], i
+    assert (ex._waits, ex._needs_event, ex._side_tail) == L.sync_plan(bare, ex.multi_stream) == L.sync_plan(ops, ex.multi_stream)
+    assert L.sync_plan(bare, True) == L.sync_plan(ops, True)          # (the fork of PPYOLO_HIP_STREAMS=2, derived only)
+
+
 def test_forward_beside_open_tickets():
     """InFlight owns its executors: a plain model(x) call while tickets are open neither disturbs the batches in flight
     nor is disturbed by them (lane 0 used to be the executor of forward itself)."""
@@ -676,7 +713,7 @@ def test_fresh_process_build_then_smoke():
 
 
 def test_vd_shortcut_pool_is_written_by_its_producer(monkeypatch):
-    """HipExecutor._link_pools: the AvgPool2d(2, 2) in front of the stage-3 / stage-4 projection shortcuts of ResNet50-vd belongs
+    """plan_links.link_pools: the AvgPool2d(2, 2) in front of the stage-3 / stage-4 projection shortcuts of ResNet50-vd belongs
     to the launch of the stage-2 / stage-3 convolution that produces its input; on the streaming kernel (csrc/conv_stream.hip) that launch
     writes the average from its epilogue, on any other tile the pooling kernel follows it.  The detections are EQUAL to
     those of the plan with the separate pooling op (PPYOLO_HIP_POOL_FOLD=0) either way -- same sums in the same order."""
@@ -735,7 +772,7 @@ def test_shortcut_fold_same_detections(monkeypatch):
 
 
 def test_maxpool_fold_same_bits(monkeypatch):
-    """Round 4 (engine._link_maxpools): the stem's max pool written by the epilogue of the convolution in front of it against the plan
+    """Round 4 (plan_links.link_maxpools): the stem's max pool written by the epilogue of the convolution in front of it against the plan
     with the pooling launch: one launch fewer, and EVERYTHING downstream equal bit for bit (same products in the same order per
     pixel, exact maxima, the same tracked maximum) -- both model families."""
     x, ims = synth.synth_images(2, 320).cuda(), synth.synth_im_size(2).cuda()

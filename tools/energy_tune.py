@@ -98,9 +98,7 @@ def main():
         rows = []
         for ms, c, s in front:
             op['cfg'], op['splitk'] = c, s
-            op.pop('x_split', None)
-            if op.get('gp_in') and s <= 1 and ex.split_capable(c, True):
-                op['x_split'] = gp_scales
+            ex._measure_form(op, gp_scales)          # (pre-split input where the layer will get one: the executor's rule)
             us, w, f, ns = energy(op)
             rows.append(dict(cfg=c, splitk=s, tune_ms=round(ms, 4), us=round(us, 2), watts=round(w or -1, 1), sclk=round(f or -1), mj=round((w or 0) * us * 1e-3, 3)))
         op.pop('x_split', None)
