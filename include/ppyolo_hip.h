@@ -663,6 +663,67 @@ int ppy_jpeg_pack_table(int n, const ppy_jpeg_desc_t *h_descs, unsigned char *co
 int ppy_jpeg_reconstruct_u8(int n, const ppy_jpeg_desc_t *h_descs, int apply_orientation, const void *table, const int16_t *coef,
                             size_t coef_bytes, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Device entropy stage (opt-in): the host keeps one linear pass per file, the GPU decodes the Huffman bits into the same
+ * coefficient buffer ppy_jpeg_entropy_decode fills, element for element.  DESIGN.md section 10.
+ *
+ * ppy_jpeg_scan_prepare (host, stateless, any thread, no GPU call) parses the markers exactly as ppy_jpeg_info does (same
+ * refusals and reasons), fills h_desc exactly as ppy_jpeg_entropy_decode does (coef_base is preserved), and writes the SCAN
+ * RECORD of the file into h_scan (16-byte aligned, at least ppy_jpeg_scan_bytes(h_data, bytes, NULL) bytes; that bound is
+ * 0 for a file ppy_jpeg_info refuses, and *h_segments, when given, receives the number of restart segments it allows for):
+ *   ppy_jpeg_scan_t | compact Huffman tables, DC then AC of each component (1424 bytes each: uint16 look[512] = length << 8 |
+ *   symbol of the 9-bit lookahead, int32 maxcode[18], int32 valoff[18], uint8 vals[256]) | segment table, 4 x uint32 each:
+ *   byte offset into the data, bit length, first MCU, MCU count | the entropy-coded bytes WITHOUT the stuffed 00 after FF,
+ *   cut at the restart markers, every segment starting on a 4-byte boundary and zero-padded to the next.
+ * The offsets in ppy_jpeg_scan_t are bytes from the start of the record.  Stream rules, those of the host decoder: a segment's
+ * data ends at the first FF not followed by 00 or at the end of the file; FF fill bytes may precede a restart marker;
+ * restart marker k must be D0 + (k & 7), a wrong or missing one is PPY_ERR_CORRUPT here; whatever follows the last
+ * segment's data, a missing EOI included, is accepted.  *h_used receives the record's size.  h_reason: NULL or 64 chars.
+ *
+ * ppy_jpeg_entropy_plan (host) lays a batch out for one subsequence size: subseq_bytes is a power of two from
+ * PPY_JPEG_SUBSEQ_MIN to PPY_JPEG_SUBSEQ_MAX (0 = PPY_JPEG_SUBSEQ_DEFAULT).  h_scan is the host copy of the scan buffer,
+ * h_scan_off[i] the byte offset of image i's record in it (% 16 == 0).  It writes the plan (ppy_jpeg_entropy_plan_bytes(n,
+ * total segments) bytes, 16-byte aligned: 64 bytes per image, then each image's first-subsequence index per segment) and
+ * returns the workspace size of the decode in *h_ws_bytes.
+ *
+ * ppy_jpeg_entropy_device enqueues a FIXED number of launches on `stream`, whatever the images, with no host
+ * synchronisation: zero the coefficients and the status words; decode every subsequence from an assumed state and
+ * synchronise the states inside each workgroup; link the workgroups and prefix-sum the slot counts; decode again from the
+ * true states, writing non-zero coefficients and DC differences; turn the DC differences into values (segmented scan per
+ * component, reset at every restart segment, modulo 2^32 truncated to int16).  plan, scan, coef, status and ws are DEVICE
+ * pointers (16-byte aligned; plan and scan are the copies of h_plan and the scan buffer); h_plan sizes the grids.
+ * status: 3 * n ints -- [0, n) PPY_OK or PPY_ERR_CORRUPT per image, [n, 2n) a reason id for ppy_jpeg_reason_string, [2n, 3n)
+ * how many subsequences' entry states only the cross-workgroup step fixed.  The status class equals the host decoder's on
+ * every input; the coefficients of an image with a non-OK status are unspecified (every write stays inside the image's own
+ * range).  TRUST BOUNDARY as for ppy_jpeg_reconstruct_u8: plan and scan must be what the two host calls wrote.
+ *
+ * ppy_jpeg_entropy_twin is the same decoder on the host, lane by lane over host memory, through the same decode step,
+ * state comparison and slot-to-address map: same arguments (all pointers HOST pointers, no stream), same outputs.  Slow;
+ * it exists so that damaged inputs can be swept without a GPU (tools/jpeg_twin_asan.cpp). */
+#define PPY_JPEG_SUBSEQ_MIN 8
+#define PPY_JPEG_SUBSEQ_MAX 4096
+#define PPY_JPEG_SUBSEQ_DEFAULT 32
+typedef struct ppy_jpeg_scan_t {
+    int components, mcus_w, mcus_h, restart_interval;
+    int h_samp[3], v_samp[3], blocks_w[3];
+    int segments, mcus;               /* restart segments; MCUs of the image */
+    int reserved;
+    long long coef_offset[3];         /* as in ppy_jpeg_desc_t */
+    long long coef_elems;
+    unsigned int table_offset, segment_offset, data_offset, data_bytes, record_bytes, reserved2;
+} ppy_jpeg_scan_t;
+size_t ppy_jpeg_scan_bytes(const unsigned char *h_data, size_t bytes, long long *h_segments);
+int ppy_jpeg_scan_prepare(const unsigned char *h_data, size_t bytes, void *h_scan, size_t scan_bytes, size_t *h_used,
+                          ppy_jpeg_desc_t *h_desc, char *h_reason);
+size_t ppy_jpeg_entropy_plan_bytes(int n, long long segments);
+int ppy_jpeg_entropy_plan(int n, const ppy_jpeg_desc_t *h_descs, const void *h_scan, size_t scan_bytes, const long long *h_scan_off,
+                          int subseq_bytes, void *h_plan, size_t plan_bytes, size_t *h_ws_bytes);
+int ppy_jpeg_entropy_device(int n, const void *h_plan, const void *plan, const void *scan, int subseq_bytes, int16_t *coef,
+                            size_t coef_bytes, int *status, void *ws, size_t ws_bytes, void *stream);
+int ppy_jpeg_entropy_twin(int n, const void *h_plan, const void *plan, const void *scan, int subseq_bytes, int16_t *coef,
+                          size_t coef_bytes, int *status, void *ws, size_t ws_bytes);
+const char *ppy_jpeg_reason_string(int reason);
+
 #ifdef __cplusplus
 }
 #endif

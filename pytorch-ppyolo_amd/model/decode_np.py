@@ -40,14 +40,17 @@ class Decode(object):
         preds = self._yolo(pimage, im_size)
         return [self._split(p.cpu().detach().numpy()) for p in preds]
 
-    def detect_files(self, paths_or_bytes):
+    def detect_files(self, paths_or_bytes, decoder=None):
         """demo.py's loop from the files themselves: JPEG paths / byte strings -> decoded on the device
         (ppyolo_hip/jpeg.py, the pixels cv2.imread gives) -> detect_raw.  A file outside the decoder's subset raises
-        PPYoloHipError naming the reason."""
-        if self._jpeg is None:
-            from ppyolo_hip.jpeg import JpegDecoder
-            self._jpeg = JpegDecoder()
-        return self.detect_raw(self._jpeg.decode(list(paths_or_bytes)))
+        PPYoloHipError naming the reason.  decoder: a JpegDecoder of the caller's (JpegDecoder(entropy='device'), say);
+        default one of this object's own with the default settings."""
+        if decoder is None:
+            if self._jpeg is None:
+                from ppyolo_hip.jpeg import JpegDecoder
+                self._jpeg = JpegDecoder()
+            decoder = self._jpeg
+        return self.detect_raw(decoder.decode(list(paths_or_bytes)))
 
     def predict(self, image, im_size):
         """numpy [N,3,S,S] f32 + numpy [N,2] (h, w) -> list of numpy [K,6] f32."""

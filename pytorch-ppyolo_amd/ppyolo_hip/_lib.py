@@ -38,6 +38,18 @@ class JpegInfo(ctypes.Structure):
                 ('reason', ctypes.c_char * 64)]
 
 
+class JpegScan(ctypes.Structure):
+    """ppy_jpeg_scan_t (include/ppyolo_hip.h): the header of a scan record."""
+    _fields_ = [('components', c_int), ('mcus_w', c_int), ('mcus_h', c_int), ('restart_interval', c_int), ('h_samp', c_int * 3),
+                ('v_samp', c_int * 3), ('blocks_w', c_int * 3), ('segments', c_int), ('mcus', c_int), ('reserved', c_int),
+                ('coef_offset', c_longlong * 3), ('coef_elems', c_longlong), ('table_offset', ctypes.c_uint),
+                ('segment_offset', ctypes.c_uint), ('data_offset', ctypes.c_uint), ('data_bytes', ctypes.c_uint),
+                ('record_bytes', ctypes.c_uint), ('reserved2', ctypes.c_uint)]
+
+
+JPEG_SUBSEQ_MIN, JPEG_SUBSEQ_MAX, JPEG_SUBSEQ_DEFAULT = 8, 4096, 32      # PPY_JPEG_SUBSEQ_* (include/ppyolo_hip.h)
+
+
 class JpegDesc(ctypes.Structure):
     """ppy_jpeg_desc_t (include/ppyolo_hip.h)."""
     _fields_ = [('width', c_int), ('height', c_int), ('components', c_int), ('orientation', c_int), ('h_samp', c_int * 3),
@@ -161,6 +173,14 @@ _PROTOS = {
     'ppy_jpeg_pack_table': (c_int, [c_int, ctypes.POINTER(JpegDesc), ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_int,
                                     c_void_p, c_size_t]),
     'ppy_jpeg_reconstruct_u8': (c_int, [c_int, ctypes.POINTER(JpegDesc), c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    'ppy_jpeg_scan_bytes': (c_size_t, [c_void_p, c_size_t, ctypes.POINTER(c_longlong)]),
+    'ppy_jpeg_scan_prepare': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), ctypes.POINTER(JpegDesc), c_void_p]),
+    'ppy_jpeg_entropy_plan_bytes': (c_size_t, [c_int, c_longlong]),
+    'ppy_jpeg_entropy_plan': (c_int, [c_int, ctypes.POINTER(JpegDesc), c_void_p, c_size_t, ctypes.POINTER(c_longlong), c_int, c_void_p,
+                                      c_size_t, ctypes.POINTER(c_size_t)]),
+    'ppy_jpeg_entropy_device': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ppy_jpeg_entropy_twin': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
+    'ppy_jpeg_reason_string': (ctypes.c_char_p, [c_int]),
 }
 
 

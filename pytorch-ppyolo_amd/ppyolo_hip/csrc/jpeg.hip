@@ -10,7 +10,8 @@
 //   jpeg_idct_kernel    dequantise + 8x8 inverse DCT, 8 lanes per block, into block-padded component planes (workspace);
 //   jpeg_colour_kernel  upsample + YCbCr -> BGR + orientation + store into the caller's HWC tensors.
 // The per-image descriptors travel as a table in device memory (packed on the host, copied with the coefficients), like the
-// blob of augment.hip.  A device entropy decoder could later fill the same coefficient buffer.
+// blob of augment.hip.  The opt-in device entropy mode fills the same coefficient buffer on the GPU (jpeg_entropy.hip); its
+// host part, one linear pass per file that writes a scan record (jpeg_scan.h), is ppy_jpeg_scan_prepare below.
 #include <string.h>
 
 #include <cstdio>
@@ -27,6 +28,7 @@
         if (!(cond)) return PPY_ERR_BAD_ARG; \
     } while (0)
 #endif
+#include "jpeg_scan.h"
 
 namespace {
 
@@ -553,6 +555,25 @@ long long planes_bytes(const ppy_jpeg_desc_t &d) {      // every plane a multipl
 
 }  // namespace
 
+static void fill_desc(const Parsed &P, ppy_jpeg_desc_t *h_desc) {      // everything but coef_base, which is the caller's
+    const long long base = h_desc->coef_base;
+    memset(h_desc, 0, sizeof(*h_desc));
+    h_desc->coef_base = base;
+    h_desc->width = P.W;
+    h_desc->height = P.H;
+    h_desc->components = P.ncomp;
+    h_desc->orientation = P.orientation;
+    h_desc->coef_bytes = P.coef_elems * 2;
+    for (int c = 0; c < P.ncomp; ++c) {
+        h_desc->h_samp[c] = P.h[c];
+        h_desc->v_samp[c] = P.v[c];
+        h_desc->blocks_w[c] = P.bw[c];
+        h_desc->blocks_h[c] = P.bh[c];
+        h_desc->coef_offset[c] = P.coef_off[c];
+        for (int k = 0; k < 64; ++k) h_desc->quant[c][stored_index(k)] = P.q[P.tq[c]][k];
+    }
+}
+
 static void fill_info(const Parsed &P, ppy_jpeg_info_t *info) {
     info->width = P.W;
     info->height = P.H;
@@ -595,22 +616,124 @@ extern "C" int ppy_jpeg_entropy_decode(const unsigned char *h_data, size_t bytes
     }
     if (h_reason) memcpy(h_reason, f.reason, sizeof(f.reason));
     if (rc != PPY_OK) return rc;
-    const long long base = h_desc->coef_base;
-    memset(h_desc, 0, sizeof(*h_desc));
-    h_desc->coef_base = base;
-    h_desc->width = P.W;
-    h_desc->height = P.H;
-    h_desc->components = P.ncomp;
-    h_desc->orientation = P.orientation;
-    h_desc->coef_bytes = P.coef_elems * 2;
-    for (int c = 0; c < P.ncomp; ++c) {
-        h_desc->h_samp[c] = P.h[c];
-        h_desc->v_samp[c] = P.v[c];
-        h_desc->blocks_w[c] = P.bw[c];
-        h_desc->blocks_h[c] = P.bh[c];
-        h_desc->coef_offset[c] = P.coef_off[c];
-        for (int k = 0; k < 64; ++k) h_desc->quant[c][stored_index(k)] = P.q[P.tq[c]][k];
+    fill_desc(P, h_desc);
+    return PPY_OK;
+}
+
+// ------------------------------------------------------------------------------- host pre-pass of the device entropy mode
+// Restart segments the file can hold: every segment but the last ends in a two-byte marker, so a file with fewer bytes
+// than that is refused ("restart marker expected") before anything is sized from its header.
+static long long scan_segments(const Parsed &P, size_t bytes) {
+    const long long mcus = (long long)P.mcux * P.mcuy, want = P.dri ? (mcus + P.dri - 1) / P.dri : 1;
+    const long long room = 1 + (long long)((bytes - P.data) / 2);
+    return want < room ? want : room;
+}
+static size_t scan_bound(const Parsed &P, size_t bytes, long long nseg) {
+    const size_t fixed = sizeof(ppy_jpeg_scan_t) + 2 * (size_t)P.ncomp * sizeof(JpegHuffDev);
+    return (fixed + (size_t)nseg * (sizeof(JpegSeg) + 4) + (bytes - P.data) + 15) / 16 * 16;
+}
+
+extern "C" size_t ppy_jpeg_scan_bytes(const unsigned char *h_data, size_t bytes, long long *h_segments) {
+    if (h_segments) *h_segments = 0;
+    if (h_data == nullptr || bytes >= (1u << 28)) return 0;
+    Parsed P;
+    Fail f = {PPY_OK, ""};
+    if (parse(h_data, bytes, P, f) != PPY_OK) return 0;
+    const long long nseg = scan_segments(P, bytes);
+    if (h_segments) *h_segments = nseg;
+    return scan_bound(P, bytes, nseg);
+}
+
+static void pack_huff(const HuffTab &t, JpegHuffDev &o) {
+    for (int i = 0; i < 512; ++i) o.look[i] = (uint16_t)(t.look_len[i] << 8 | t.look_sym[i]);
+    for (int l = 0; l < 18; ++l) {
+        o.maxcode[l] = t.maxcode[l];
+        o.valoff[l] = t.valoff[l];
     }
+    memcpy(o.vals, t.vals, 256);
+}
+
+extern "C" int ppy_jpeg_scan_prepare(const unsigned char *h_data, size_t bytes, void *h_scan, size_t scan_bytes, size_t *h_used,
+                                     ppy_jpeg_desc_t *h_desc, char *h_reason) {
+    if (h_reason) h_reason[0] = 0;
+    if (h_used) *h_used = 0;
+    if (h_data == nullptr || h_scan == nullptr || h_desc == nullptr || ((uintptr_t)h_scan & 15) != 0 || bytes >= (1u << 28)) return PPY_ERR_BAD_ARG;
+    Parsed P;
+    Fail f = {PPY_OK, ""};
+    int rc = parse(h_data, bytes, P, f);
+    const unsigned char *d = h_data;
+    const size_t n = bytes;
+    if (rc == PPY_OK) {
+        const long long mcus = (long long)P.mcux * P.mcuy, nseg = P.dri ? (mcus + P.dri - 1) / P.dri : 1;
+        if (nseg != scan_segments(P, n)) rc = fail(f, PPY_ERR_CORRUPT, "restart marker expected");
+        else if (scan_bound(P, n, nseg) > scan_bytes) rc = fail(f, PPY_ERR_WORKSPACE, "scan buffer too small");
+        else {
+            unsigned char *rec = static_cast<unsigned char *>(h_scan);
+            ppy_jpeg_scan_t H;
+            memset(&H, 0, sizeof(H));
+            H.components = P.ncomp;
+            H.mcus_w = P.mcux;
+            H.mcus_h = P.mcuy;
+            H.restart_interval = P.dri;
+            H.segments = (int)nseg;
+            H.mcus = (int)mcus;
+            H.coef_elems = P.coef_elems;
+            for (int c = 0; c < P.ncomp; ++c) {
+                H.h_samp[c] = P.h[c];
+                H.v_samp[c] = P.v[c];
+                H.blocks_w[c] = P.bw[c];
+                H.coef_offset[c] = P.coef_off[c];
+            }
+            H.table_offset = (unsigned)sizeof(H);
+            H.segment_offset = H.table_offset + 2 * (unsigned)P.ncomp * (unsigned)sizeof(JpegHuffDev);
+            H.data_offset = H.segment_offset + (unsigned)nseg * (unsigned)sizeof(JpegSeg);
+            JpegHuffDev *tabs = reinterpret_cast<JpegHuffDev *>(rec + H.table_offset);
+            for (int c = 0; c < P.ncomp; ++c) {
+                pack_huff(P.dc[P.td[c]], tabs[c]);
+                pack_huff(P.ac[P.ta[c]], tabs[P.ncomp + c]);
+            }
+            JpegSeg *seg = reinterpret_cast<JpegSeg *>(rec + H.segment_offset);
+            unsigned char *out = rec + H.data_offset;
+            size_t p = P.data, o = 0;
+            for (long long s = 0; s < nseg; ++s) {
+                const size_t start = o;
+                while (p < n) {      // the one walk over the entropy-coded bytes: unstuff, stop at a marker
+                    const unsigned char c = d[p];
+                    if (c != 0xFF) {
+                        out[o++] = c;
+                        ++p;
+                    } else if (p + 1 < n && d[p + 1] == 0) {
+                        out[o++] = 0xFF;
+                        p += 2;
+                    } else break;
+                }
+                seg[s].byte_off = (uint32_t)start;
+                seg[s].bit_len = (uint32_t)((o - start) * 8);
+                seg[s].first_mcu = (uint32_t)(P.dri ? s * P.dri : 0);
+                seg[s].mcu_count = (uint32_t)(P.dri && (s + 1) * P.dri < mcus ? P.dri : mcus - (P.dri ? s * P.dri : 0));
+                while (o & 3) out[o++] = 0;
+                if (s + 1 < nseg) {
+                    while (p + 1 < n && d[p] == 0xFF && d[p + 1] == 0xFF) ++p;
+                    if (p + 1 >= n || d[p] != 0xFF || d[p + 1] != 0xD0 + (int)(s & 7)) {
+                        rc = fail(f, PPY_ERR_CORRUPT, "restart marker expected");
+                        break;
+                    }
+                    p += 2;
+                }
+            }
+            if (rc == PPY_OK) {
+                H.data_bytes = (unsigned)o;
+                const size_t used = ((size_t)H.data_offset + o + 15) / 16 * 16;
+                memset(out + o, 0, used - H.data_offset - o);
+                H.record_bytes = (unsigned)used;
+                memcpy(rec, &H, sizeof(H));
+                if (h_used) *h_used = used;
+            }
+        }
+    }
+    if (h_reason) memcpy(h_reason, f.reason, sizeof(f.reason));
+    if (rc != PPY_OK) return rc;
+    fill_desc(P, h_desc);
     return PPY_OK;
 }
 

@@ -8,6 +8,11 @@ there is no fallback).  The coefficients are written straight into one of two pi
 in one copy together with the descriptor table, so the entropy stage of the next batch overlaps the copy and the kernels of
 this one.
 
+JpegDecoder(entropy='device') moves the Huffman decoding to the GPU as well: the host keeps one linear pass per file (markers,
+unstuffing, cutting at the restart markers: ppy_jpeg_scan_prepare), the compressed bytes cross instead of the coefficients,
+and csrc/jpeg_entropy.hip fills the same coefficient buffer on the device, element for element.  Damage inside the entropy
+data is then found on the device and comes back as one status word per image.  The default stays 'host'.
+
 Baseline Huffman JPEG only (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0): anything else raises PPYoloHipError naming the reason, so a
 caller can hand that file to a decoder of its own.  A truncated or damaged file is an error too (libjpeg would fill the
 missing part with grey and warn)."""
@@ -19,7 +24,8 @@ from concurrent.futures import ThreadPoolExecutor
 import torch
 
 from . import _lib
-from ._lib import PPYoloHipError, check, lib
+from ._lib import PPYoloHipError, lib
+from ._lib import check as _check
 
 MAX_THREADS = 16
 
@@ -42,15 +48,25 @@ class HostBatch(object):
     """Output of the entropy stage: descriptors + the pinned buffer holding [descriptor table | coefficients].  It OWNS one of
     the decoder's two staging buffers until it is passed to reconstruct() (which may be repeated until a later batch takes the
     buffer) or release()d; see JpegDecoder.entropy_decode."""
-    __slots__ = ('n', 'descs', 'sizes', 'stage', 'slot', 'gen', 'table_bytes', 'total_bytes')
+    __slots__ = ('n', 'descs', 'sizes', 'stage', 'slot', 'gen', 'table_bytes', 'total_bytes', 'entropy', 'scan_off', 'plan_bytes',
+                 'scan_bytes', 'coef_bytes', 'status')
 
 
 class JpegDecoder(object):
-    def __init__(self, device='cuda', threads=None, apply_orientation=True, max_pixels=1 << 28):
-        """threads: workers of the entropy stage, default min(16, images of the call); never more than 16, never derived from
+    def __init__(self, device='cuda', threads=None, apply_orientation=True, max_pixels=1 << 28, entropy='host', subseq_bytes=None):
+        """entropy: 'host' (Huffman decoding on the thread pool) or 'device' (on the GPU; the pool runs the marker pass alone).
+        subseq_bytes: device mode, bytes of compressed data per lane, a power of two in [8, 4096]; default 32 (8 and 16 decode faster in isolation: profiles/jpeg_bench_device_entropy.txt).
+        threads: workers of the entropy stage, default min(16, images of the call); never more than 16, never derived from
         the machine's CPU count.  apply_orientation=False delivers the stored raster (cv2.IMREAD_IGNORE_ORIENTATION).
         max_pixels: a header that claims more is refused before any buffer is sized from it (a few bytes can claim 65535 x 65535)."""
         self.max_pixels = int(max_pixels)
+        if entropy not in ('host', 'device'):
+            raise PPYoloHipError("entropy must be 'host' or 'device', got %r" % (entropy,))
+        self.entropy = entropy
+        self.subseq_bytes = _lib.JPEG_SUBSEQ_DEFAULT if subseq_bytes is None else int(subseq_bytes)
+        if not (_lib.JPEG_SUBSEQ_MIN <= self.subseq_bytes <= _lib.JPEG_SUBSEQ_MAX) or self.subseq_bytes & (self.subseq_bytes - 1):
+            raise PPYoloHipError('subseq_bytes must be a power of two in [%d, %d]' % (_lib.JPEG_SUBSEQ_MIN, _lib.JPEG_SUBSEQ_MAX))
+        self.last_status = None         # device mode: the status tensor of the last reconstruct()
         self.device = torch.device(device)
         if threads is not None and threads < 1:
             raise PPYoloHipError('threads must be >= 1')
@@ -106,6 +122,8 @@ class JpegDecoder(object):
         n = len(datas)
         if n == 0:
             raise PPYoloHipError('empty batch')
+        if self.entropy == 'device':
+            return self._scan_prepare(datas)
         descs = (_lib.JpegDesc * n)()
         sizes = []
         table_bytes = L.ppy_jpeg_table_bytes(n)
@@ -123,6 +141,7 @@ class JpegDecoder(object):
         slot, gen, stage = self._staging(total)
         hb = HostBatch()
         hb.n, hb.descs, hb.sizes, hb.stage, hb.slot, hb.gen, hb.table_bytes, hb.total_bytes = n, descs, sizes, stage, slot, gen, table_bytes, total
+        hb.entropy, hb.status = 'host', None
         base = stage.data_ptr() + table_bytes
 
         def one(i):
@@ -139,10 +158,68 @@ class JpegDecoder(object):
             raise
         return hb
 
+    def _scan_prepare(self, datas):
+        """entropy_decode() of the device mode: the marker pass of every item writes its scan record into the staging buffer,
+        laid out [descriptor table | plan | records]; the coefficients only ever exist on the device."""
+        L = lib()
+        n = len(datas)
+        descs = (_lib.JpegDesc * n)()
+        sizes, scan_off, bounds = [], [], []
+        coef_bytes = scan_bytes = segments = 0
+
+        def size(i):          # the two header-only calls that size the buffers, on the pool like the pass itself
+            info, segs = _lib.JpegInfo(), ctypes.c_longlong()
+            rc = L.ppy_jpeg_info(datas[i], len(datas[i]), ctypes.byref(info))
+            bound = L.ppy_jpeg_scan_bytes(datas[i], len(datas[i]), ctypes.byref(segs)) if rc == _lib.OK else 0
+            return rc, info, bound, segs
+
+        for i, (rc, info, bound, segs) in enumerate(self._map(size, n)):
+            d = datas[i]
+            if rc != _lib.OK:
+                raise _refuse(i, rc, info.reason)
+            if info.width * info.height > self.max_pixels:
+                raise PPYoloHipError('item %d: %d x %d pixels is over max_pixels = %d' % (i, info.width, info.height, self.max_pixels))
+            if bound == 0:
+                raise PPYoloHipError('item %d: file of %d bytes is too large for the device entropy stage' % (i, len(d)))
+            descs[i].coef_base = coef_bytes
+            coef_bytes += (info.coef_bytes + 15) // 16 * 16
+            scan_off.append(scan_bytes)
+            bounds.append(bound)
+            scan_bytes += bound
+            segments += segs.value
+            sizes.append((info.height, info.width, info.out_height, info.out_width, info.coef_bytes))
+        table_bytes = L.ppy_jpeg_table_bytes(n)
+        plan_bytes = L.ppy_jpeg_entropy_plan_bytes(n, segments)
+        total = table_bytes + plan_bytes + scan_bytes
+        slot, gen, stage = self._staging(total)
+        hb = HostBatch()
+        hb.n, hb.descs, hb.sizes, hb.stage, hb.slot, hb.gen, hb.table_bytes, hb.total_bytes = n, descs, sizes, stage, slot, gen, table_bytes, total
+        hb.entropy, hb.status, hb.scan_off, hb.plan_bytes, hb.scan_bytes, hb.coef_bytes = 'device', None, scan_off, plan_bytes, scan_bytes, coef_bytes
+        base = stage.data_ptr() + table_bytes + plan_bytes
+
+        def one(i):
+            reason = ctypes.create_string_buffer(64)
+            rc = L.ppy_jpeg_scan_prepare(datas[i], len(datas[i]), base + scan_off[i], bounds[i], None, ctypes.byref(descs[i]), reason)
+            return rc, reason.value
+
+        try:
+            for i, (rc, reason) in enumerate(self._map(one, n)):
+                if rc != _lib.OK:
+                    raise _refuse(i, rc, reason)
+        except BaseException:
+            self.release(hb)
+            raise
+        return hb
+
     # ---- device stage -------------------------------------------------------------------------------------------------
-    def reconstruct(self, hb, out=None):
+    def reconstruct(self, hb, out=None, check=True):
         """Copy a HostBatch to the device and enqueue the two reconstruction launches on the current stream.  out: optional
-        list of uint8 device tensors [h,w,3] to fill (pixel stride 3, any row stride)."""
+        list of uint8 device tensors [h,w,3] to fill (pixel stride 3, any row stride).
+        A batch of the device entropy mode: the copy carries the compressed data, the entropy launches come before the two
+        reconstruction launches, and with check=True (the default) the n status words are read back in one small copy, which
+        synchronises the stream once: damage raises PPYoloHipError naming the item, as the host mode does in entropy_decode().
+        check=False reads nothing back; hb.status (and self.last_status) is the int32 device tensor [3, n] of status codes,
+        reason ids (ppy_jpeg_reason_string) and cross-workgroup repair counts, for the caller to examine later."""
         L = lib()
         n = hb.n
         ori = self.apply_orientation
@@ -162,11 +239,29 @@ class JpegDecoder(object):
             busy = self._busy[hb.slot]
         if busy is not None:                    # the same HostBatch again: its last copy still reads the table
             busy.synchronize()
-        check(L.ppy_jpeg_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
-                                    (ctypes.c_longlong * n)(*[max(t.stride(0), 3 * t.shape[1]) for t in out]), int(ori),
-                                    hb.stage.data_ptr(), hb.table_bytes), 'ppy_jpeg_pack_table')
+        _check(L.ppy_jpeg_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
+                                     (ctypes.c_longlong * n)(*[max(t.stride(0), 3 * t.shape[1]) for t in out]), int(ori),
+                                     hb.stage.data_ptr(), hb.table_bytes), 'ppy_jpeg_pack_table')
+        device_entropy = hb.entropy == 'device'
+        if device_entropy:
+            h_plan = hb.stage.data_ptr() + hb.table_bytes
+            ent_ws = ctypes.c_size_t()
+            _check(L.ppy_jpeg_entropy_plan(n, hb.descs, h_plan + hb.plan_bytes, hb.scan_bytes, (ctypes.c_longlong * n)(*hb.scan_off),
+                                           self.subseq_bytes, h_plan, hb.plan_bytes, ctypes.byref(ent_ws)), 'ppy_jpeg_entropy_plan')
         blob = torch.empty(hb.total_bytes, dtype=torch.uint8, device=self.device)
         blob.copy_(hb.stage[:hb.total_bytes], non_blocking=True)
+        stream = torch.cuda.current_stream().cuda_stream
+        if device_entropy:      # enqueued before the staging buffer is given back: the call sizes its grids from the host plan
+            coef = torch.empty(max(hb.coef_bytes, 16), dtype=torch.uint8, device=self.device)
+            coef_ptr, coef_bytes = coef.data_ptr(), hb.coef_bytes
+            status = torch.empty((3, n), dtype=torch.int32, device=self.device)
+            ent = torch.empty(max(ent_ws.value, 16), dtype=torch.uint8, device=self.device)
+            _check(L.ppy_jpeg_entropy_device(n, h_plan, blob.data_ptr() + hb.table_bytes, blob.data_ptr() + hb.table_bytes + hb.plan_bytes,
+                                             self.subseq_bytes, coef_ptr, coef_bytes, status.data_ptr(), ent.data_ptr(), ent_ws.value, stream),
+                   'ppy_jpeg_entropy_device')
+            hb.status = self.last_status = status
+        else:
+            coef_ptr, coef_bytes = blob.data_ptr() + hb.table_bytes, hb.total_bytes - hb.table_bytes
         ev = torch.cuda.Event()
         ev.record()
         with self._lock:
@@ -174,14 +269,20 @@ class JpegDecoder(object):
             self._held[hb.slot] = False
         ws_bytes = L.ppy_jpeg_workspace_bytes(n, hb.descs)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        check(L.ppy_jpeg_reconstruct_u8(n, hb.descs, int(ori), blob.data_ptr(), blob.data_ptr() + hb.table_bytes, hb.total_bytes - hb.table_bytes,
-                                        ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream), 'ppy_jpeg_reconstruct_u8')
+        _check(L.ppy_jpeg_reconstruct_u8(n, hb.descs, int(ori), blob.data_ptr(), coef_ptr, coef_bytes, ws.data_ptr(), ws_bytes, stream),
+               'ppy_jpeg_reconstruct_u8')
+        if device_entropy and check:
+            st = status.cpu()          # one small copy; it waits for the stream
+            for i in range(n):
+                if int(st[0, i]) != _lib.OK:
+                    raise _refuse(i, int(st[0, i]), L.ppy_jpeg_reason_string(int(st[1, i])))
         return out
 
     # ---- the user's calls ---------------------------------------------------------------------------------------------
-    def decode(self, items, out=None):
-        """list of bytes / memoryview / paths -> list of uint8 [h,w,3] BGR device tensors, asynchronous on the current stream."""
-        return self.reconstruct(self.entropy_decode(items), out=out)
+    def decode(self, items, out=None, check=True):
+        """list of bytes / memoryview / paths -> list of uint8 [h,w,3] BGR device tensors, asynchronous on the current stream
+        (the device entropy mode with check=True waits for its status words: reconstruct())."""
+        return self.reconstruct(self.entropy_decode(items), out=out, check=check)
 
     def imdecode(self, buf):
         return self.decode([buf])[0]

@@ -1,6 +1,6 @@
 """JPEG decoder timings (ppyolo_hip/jpeg.py, csrc/jpeg.hip).
 
-    python tools/jpeg_bench.py [--bs 8] [--window 1.0] [--rounds 5] [--no-model]
+    python tools/jpeg_bench.py [--bs 8] [--window 1.0] [--rounds 5] [--no-model] [--entropy {host,device}]
 
 Input: the COCO-sized files of tests/golden/g20_jpeg.npz replicated to a batch.  Reports
   entropy_ms_per_image   host stage (parse + Huffman) at 1 and 16 threads, wall clock over 4 batches per call;
@@ -11,6 +11,11 @@ Input: the COCO-sized files of tests/golden/g20_jpeg.npz replicated to a batch. 
                          own, one batch ahead, beside detect_raw on the same images already decoded, alternating in one run;
                          and, to attribute a gap, detect_raw beside the entropy stage alone and beside copy + kernels alone;
   pillow_ms_per_image    Pillow's (libjpeg-turbo's) decode of the same files at 1 and 16 threads, where Pillow is installed.
+--entropy device adds the device entropy mode (JpegDecoder(entropy='device'), csrc/jpeg_entropy.hip) to the same run:
+  device_entropy         prepass_ms_per_image: the host marker pass at 1 and 16 threads; h2d: bytes and time of its one copy
+                         (table + plan + compressed scan records); entropy_ms: the entropy launches of a batch replayed from a
+                         graph, per subsequence size, beside reconstruct.ms; link_fixed: subsequences the cross-workgroup step
+                         repaired; and in detect the legs files_device (status read back per batch) and files_device_nocheck.
 Every timed window lasts at least --window seconds (the repeat count is calibrated first); the detect legs alternate for
 --rounds rounds and report every round, so the spread is in the output.  One JSON line."""
 import argparse
@@ -79,6 +84,7 @@ def main():
     ap.add_argument('--window', type=float, default=1.0)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--no-model', action='store_true')
+    ap.add_argument('--entropy', choices=('host', 'device'), default='host')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a ROCm device'
     data = files(a.bs)
@@ -112,6 +118,44 @@ def main():
     k_ms, c_ms = replay_ms(kernels, a.window), replay_ms(lambda: dst.copy_(src), a.window)
     res['reconstruct'] = dict(ms=k_ms, coef_bytes=coef_bytes, pixel_bytes=pixel_bytes, plane_bytes=ws_bytes,
                               copy_same_bytes_ms=c_ms, images_per_s=a.bs / k_ms * 1e3)
+
+    # the device entropy mode: marker pass, copy, entropy launches
+    if a.entropy == 'device':
+        import ctypes
+        de = dict(prepass_ms_per_image={})
+        for th in (1, 16):
+            jdp = JpegDecoder(threads=th, entropy='device')
+            many = data * 4
+            de['prepass_ms_per_image'][str(th)] = wall_s(lambda: jdp.release(jdp.entropy_decode(many)), a.window) * 1e3 / len(many)
+        jde = JpegDecoder(entropy='device')
+        hbd = jde.entropy_decode(data)
+        outs_d = jde.reconstruct(hbd)
+        assert all(torch.equal(x, y) for x, y in zip(outs, outs_d)), 'device entropy mode decodes other pixels'
+        blob_d = torch.empty(hbd.total_bytes, dtype=torch.uint8, device='cuda')
+        de['h2d'] = dict(bytes=hbd.total_bytes, ms=event_ms(lambda: blob_d.copy_(hbd.stage[:hbd.total_bytes], non_blocking=True), a.window))
+        h_plan = hbd.stage.data_ptr() + hbd.table_bytes
+        coef_d = torch.empty(hbd.coef_bytes, dtype=torch.uint8, device='cuda')
+        status = torch.empty((3, hbd.n), dtype=torch.int32, device='cuda')
+        de['entropy_ms'], de['link_fixed'], de['subsequences'] = {}, {}, {}
+        for sub in (8, 16, 32, 64, 128, 256, 1024):
+            wsb = ctypes.c_size_t()
+            _lib.check(L.ppy_jpeg_entropy_plan(hbd.n, hbd.descs, h_plan + hbd.plan_bytes, hbd.scan_bytes, (ctypes.c_longlong * hbd.n)(*hbd.scan_off),
+                                               sub, h_plan, hbd.plan_bytes, ctypes.byref(wsb)), 'ppy_jpeg_entropy_plan')
+            blob_d.copy_(hbd.stage[:hbd.total_bytes])
+            torch.cuda.synchronize()
+            ews = torch.empty(max(wsb.value, 16), dtype=torch.uint8, device='cuda')
+
+            def entropy():
+                _lib.check(L.ppy_jpeg_entropy_device(hbd.n, h_plan, blob_d.data_ptr() + hbd.table_bytes,
+                                                     blob_d.data_ptr() + hbd.table_bytes + hbd.plan_bytes, sub, coef_d.data_ptr(), hbd.coef_bytes,
+                                                     status.data_ptr(), ews.data_ptr(), wsb.value, torch.cuda.current_stream().cuda_stream),
+                           'ppy_jpeg_entropy_device')
+            de['entropy_ms'][str(sub)] = replay_ms(entropy, a.window / 4)
+            assert not status[:2].any().item()
+            de['link_fixed'][str(sub)] = int(status[2].sum().item())
+            de['subsequences'][str(sub)] = wsb.value // 24
+        jde.release(hbd)
+        res['device_entropy'] = de
 
     # files -> detections, beside pre-decoded pixels -> detections
     if not a.no_model:
@@ -165,6 +209,18 @@ def main():
         jd_host = JpegDecoder()
         legs = [('raw', raw_fed), ('files', fed(produce_all)), ('raw_beside_entropy_stage', fed(produce_host_only)),
                 ('raw_beside_copy_and_kernels', fed(produce_device_only))]
+        if a.entropy == 'device':
+            jd_e = JpegDecoder(entropy='device')
+
+            def produce_device_entropy(check):
+                def produce():
+                    with torch.cuda.stream(side):
+                        imgs = jd_e.decode(data, check=check)
+                        ev = torch.cuda.Event()
+                        ev.record(side)
+                    return imgs, ev
+                return produce
+            legs += [('files_device', fed(produce_device_entropy(True))), ('files_device_nocheck', fed(produce_device_entropy(False)))]
         for _, fn in legs:
             fn(3)
         torch.cuda.synchronize()
