@@ -17,6 +17,8 @@
 //   * the IoU-aware term's reduction over grid x before the multiplication with tobj (iou_losses.py:241-242):
 //     loss = sum_h (sum_w tobj[h,w]) * (sum_w' iou[h,w'] * -log(ioup[h,w'] + 1e-9)),
 //   * `+ 1e-9` INSIDE the logarithms, `+ 1e-10` in the IoU union of the IoU losses and none in the ignore-mask IoU,
+//   * the Grid Sensitive offset 0.5 * (scale_x_y - 1) as the reference's Python scalar: evaluated in double, rounded to float32
+//     once (0.5f * (1.05f - 1.0f) is one ulp of px away from it: |px - tx| then ties where the reference's does not),
 //   * |.| gradients with sign(0) = 0, min / max ties sharing the gradient, clamp(min=0) passing it at 0 (torch autograd).
 #include "common.h"
 
@@ -30,6 +32,7 @@ struct LossArgs {
     int N, S, an, C, G, iou_aware;
     float aw[4], ah[4];
     float downsample, scale_x_y, ignore_thresh, w_iou, w_iou_aware, inv_n;
+    float xy_bias;            // 0.5 * (scale_x_y - 1) evaluated in double and rounded once, as the reference's Python scalar is
     int loss_square;          // IouLoss(loss_square=): 1 - iou^2 (both PP-YOLO configurations), or 1 - iou (reference iou_losses.py:66-70)
 };
 
@@ -116,8 +119,8 @@ __global__ void __launch_bounds__(LOSS_CELLS * LOSS_MAXAN * LOSS_Q) yolo_loss_ke
         g_x = ts * (-tx / (sx + 1e-9f) + (1.f - tx) / (1.f - sx + 1e-9f)) * sx * (1.f - sx);
         g_y = ts * (-ty / (sy + 1e-9f) + (1.f - ty) / (1.f - sy + 1e-9f)) * sy * (1.f - sy);
     } else {                                               // Grid Sensitive: L1 on the decoded offset
-        px = sxy * sx - 0.5f * (sxy - 1.0f);
-        py = sxy * sy - 0.5f * (sxy - 1.0f);
+        px = sxy * sx - p.xy_bias;
+        py = sxy * sy - p.xy_bias;
         l_xy = fabsf(px - tx) * ts + fabsf(py - ty) * ts;
         g_x = sgn(px - tx) * ts * sxy * sx * (1.f - sx);
         g_y = sgn(py - ty) * ts * sxy * sy * (1.f - sy);
@@ -177,7 +180,7 @@ __global__ void __launch_bounds__(LOSS_CELLS * LOSS_MAXAN * LOSS_Q) yolo_loss_ke
     }
 
     // ---- objectness with the ignore mask (losses.py:296-356): boxes as paddle_yolo_box decodes them (losses.py:22-83)
-    const float bx = (sxy * sx + (float)w - (sxy - 1.0f) * 0.5f) * p.downsample, by = (sxy * sy + (float)h - (sxy - 1.0f) * 0.5f) * p.downsample;
+    const float bx = (sxy * sx + (float)w - p.xy_bias) * p.downsample, by = (sxy * sy + (float)h - p.xy_bias) * p.downsample;
     const float bw = expf(lw) * aw, bh = expf(lh) * ah;
     const float q0 = (bx - bw / 2) / S / p.downsample, q1 = (by - bh / 2) / S / p.downsample;
     const float q2 = (bx + bw / 2) / S / p.downsample, q3 = (by + bh / 2) / S / p.downsample;
@@ -289,6 +292,7 @@ extern "C" int ppy_yolov3_loss_f32(const float *head_out, int out_ld, const floa
         p.ah[a] = h_anchors_px[2 * a + 1];
     }
     p.downsample = (float)downsample; p.scale_x_y = (float)scale_x_y; p.ignore_thresh = (float)ignore_thresh;
+    p.xy_bias = (float)(0.5 * (scale_x_y - 1.0));
     p.loss_square = iou_loss_square ? 1 : 0;
     p.w_iou = (float)iou_loss_weight; p.w_iou_aware = (float)iou_aware_loss_weight; p.inv_n = 1.0f / (float)N;
     // (a row must fit the staging: C up to a few hundred classes; the pair threads are LOSS_CELLS x an <= 256)
