@@ -422,6 +422,22 @@ int ppy_augment_render_f32(const void *blob, long long blob_bytes, int n, int S,
  * sample's canvas dtype); h, w, dtype must match the descriptor, otherwise nothing is written.  For pinning. */
 int ppy_augment_canvas(const void *blob, long long blob_bytes, int index, int h, int w, int dtype, void *out,
                        void *stream);
+/* The same two calls with sources that lie OUTSIDE the blob (version 102).  A descriptor whose ext0 (ext1) field is 1 names
+ * its first (mixup) source by an index into a table of n_src device images instead of a blob offset: src_ptrs[i] points to an
+ * src_h[i] x src_w[i] x 3 uint8 image (BGR, pixel stride 3) with 3 * src_w[i] <= src_pitch[i] < 2^31 bytes per row and any
+ * alignment -- a decoder's output, or a cropped view of a larger image, read where it lies.  The four arrays are HOST arrays
+ * of length n_src (n_src = 0: the calls above); a null pointer, a non-positive extent or a short pitch is PPY_ERR_BAD_ARG.
+ * The table reaches the kernels in the launch arguments, 16 entries per launch, consecutive windows sharing one entry: the
+ * two external sources of one sample must lie in one window, which adjacent entries (as augment.pack_batch emits them)
+ * always do.  A descriptor whose index is >= n_src, whose two indices share no window, or whose h0 / w0 (h1 / w1) differ
+ * from the table entry's is skipped like any other invalid descriptor.  In-blob and external sources mix freely. */
+int ppy_augment_render_src_f32(const void *blob, long long blob_bytes, int n, int S, const float *lut,
+                               const double *mean_std, int is_scale, float *out, int n_src,
+                               const unsigned char *const *src_ptrs, const long long *src_pitch, const int *src_h,
+                               const int *src_w, void *stream);
+int ppy_augment_canvas_src(const void *blob, long long blob_bytes, int index, int h, int w, int dtype, void *out,
+                           int n_src, const unsigned char *const *src_ptrs, const long long *src_pitch, const int *src_h,
+                           const int *src_w, void *stream);
 /* Dense YOLO targets: out (device float32, total elements, 16-byte aligned) is zero-filled, then out[offsets[i]] =
  * values[i] for the n host-computed elements (device arrays, offsets unique; targets.gt2yolo_records). */
 int ppy_augment_targets_f32(float *out, long long total, const long long *offsets, const float *values, int n,

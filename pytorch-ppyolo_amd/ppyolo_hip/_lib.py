@@ -131,6 +131,11 @@ _PROTOS = {
     'ppy_augment_render_f32': (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int, c_void_p,
                                         c_void_p]),
     'ppy_augment_canvas': (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    'ppy_augment_render_src_f32': (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int, c_void_p,
+                                            c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), ctypes.POINTER(c_int),
+                                            ctypes.POINTER(c_int), c_void_p]),
+    'ppy_augment_canvas_src': (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_int, ctypes.POINTER(c_void_p),
+                                        ctypes.POINTER(c_longlong), ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_void_p]),
     'ppy_augment_targets_f32': (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p]),
     'ppy_cocoeval_workspace_bytes': (c_size_t, [c_longlong] + [c_int] * 6),
     'ppy_cocoeval_records_f32': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,

@@ -17,9 +17,16 @@ sample transforms, then that sample's RandomShapeSingle interpolation draw.  (Wi
 order is nondeterministic: all its threads share the global np.random.)  The batch's `shape` is drawn by the caller
 before get_samples, as train.py:90 does.
 
+SOURCES.  A record's image (and its mixup partner's) is a numpy array, a CPU tensor -- both are packed into the blob -- or a
+uint8 [h,w,3] tensor on the builder's device with pixel stride 3 (what JpegDecoder returns, or a cropped view of a larger
+tensor): the kernels read that one where it lies, no pixel of it visits the host.  `decode_records` / `from_files` are the
+reference's DecodeImage on the device: records with 'im_file' or JPEG bytes in, device-resident images out.
+
 Settings the reference configs do not use are refused with PPYoloHipError (cutmix, hsv_format, random_channel,
 random_apply=False, resize_box, mask / keypoint fields, a dsize that is not shape x shape).
 """
+import re
+
 import numpy as np
 import torch
 
@@ -207,7 +214,8 @@ class TrainBatchBuilder(object):
     (train.py:80-88) on the device: images float32 [N,3,S,S], gt_bbox float32 [N,50,4], gt_class int32 [N,50],
     gt_score float32 [N,50], target0..L-1 float32 [N,3,6+C,S/ds,S/ds].  `samples` are records after DecodeImage with
     the image as cv2.imdecode gives it (uint8 HWC BGR): image, h, w, gt_bbox [G,4] xyxy px float32, gt_class [G,1]
-    int32, gt_score [G,1] float32, is_crowd, optional `mixup` sub-record of the same form."""
+    int32, gt_score [G,1] float32, is_crowd, optional `mixup` sub-record of the same form.  `image` may also be a tensor:
+    see `source_image`."""
 
     def __init__(self, cfg, device='cuda'):
         self.device = torch.device(device)
@@ -263,6 +271,7 @@ class TrainBatchBuilder(object):
         self.downsample_ratios, self.num_classes = g['downsample_ratios'], g['num_classes']
         self.iou_thresh = g.get('iou_thresh', 1.)
         self._lut = None
+        self._decoder = None
 
     # ---------------------------------------------------------------------------------------------------------------
     # one sample, transform by transform (the reference's classes, draw for draw; images are only their extents)
@@ -416,27 +425,23 @@ class TrainBatchBuilder(object):
         for k in ('gt_poly', 'gt_keypoint', 'cutmix', 'semantic'):
             if rec.get(k) is not None:
                 raise PPYoloHipError('field %r is not implemented (the reference configs do not use it)' % k)
-        im = rec['image']
-        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
-            raise PPYoloHipError('expected a decoded uint8 image [h, w, 3]')
+        return source_image(rec['image'], self.device)
 
     @staticmethod
-    def _fresh(rec):
+    def _fresh(rec, image):
         """A record as DecodeImage leaves it, plus the planner's image state (no pixel is touched)."""
-        s = dict(rec)
+        s = dict(rec, image=image)
         for k in ('gt_bbox', 'gt_class', 'gt_score', 'is_crowd'):
             s[k] = np.array(rec[k], copy=True)
-        s['h'], s['w'] = rec['image'].shape[:2]             # DecodeImage: h / w from the decoded image
+        s['h'], s['w'] = (int(v) for v in image.shape[:2])  # DecodeImage: h / w from the decoded image
         s.update(ops=[], mix=None, expand=None, flip=False, crop=(0, 0, s['h'], s['w']))
         return s
 
     def _plan_one(self, rec, shape, rng):
-        self._check_record(rec)
-        s = self._fresh(rec)
+        s = self._fresh(rec, self._check_record(rec))
         if 'mixup' in rec:
             if self.with_mixup:
-                self._check_record(rec['mixup'])
-                s['mixup'] = self._fresh(rec['mixup'])
+                s['mixup'] = self._fresh(rec['mixup'], self._check_record(rec['mixup']))
             else:
                 s.pop('mixup')
         for name in self.sample_seq:
@@ -504,9 +509,10 @@ class TrainBatchBuilder(object):
         images = torch.empty((N, 3, shape, shape), dtype=torch.float32, device=self.device)
         sizes = [N * len(m) * (6 + self.num_classes) * g * g for m, g in zip(self.anchor_masks, levels)]
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=self.device)
-        ops.augment_render(dev, N, shape, self._lut, self.mean, self.std, images, self.is_scale)
+        sources = self._hold(layout['sources'])
+        ops.augment_render(dev, N, shape, self._lut, self.mean, self.std, images, self.is_scale, sources=sources)
         ops.augment_targets(flat, dev, layout['toff'], layout['tval'], len(offs))
-        self._keep = (pinned, dev)       # (the blob's boxes are views into dev)
+        self._keep = (pinned, dev, sources)         # (the blob's boxes are views into dev; the launch reads the sources)
         out = dict(images=images)
         box = dev[layout['gt_bbox']:layout['gt_bbox'] + gt_bbox.nbytes].view(torch.float32).view(N, -1, 4)
         out['gt_bbox'] = box
@@ -526,8 +532,126 @@ class TrainBatchBuilder(object):
         ch, cw = recipe['crop'][2], recipe['crop'][3]
         dt = {U8: torch.uint8, F32: torch.float32, F64: torch.float64}[recipe['canvas_dtype']]
         out = torch.empty((ch, cw, 3), dtype=dt, device=self.device)
-        ops.augment_canvas(dev, 0, out)
+        ops.augment_canvas(dev, 0, out, sources=self._hold(layout['sources']))
         return out
+
+    def _hold(self, sources):
+        """External sources are read by launches on the current stream: tell the allocator, so that memory a caller drops
+        right after the call (or that another stream's decoder owns) is not handed out again under the kernel."""
+        if sources:
+            cur = torch.cuda.current_stream(self.device)
+            for t in sources:
+                t.record_stream(cur)
+        return sources
+
+    def from_files(self, records, shape, rng=np.random, decoder=None, fallback=None):
+        """`builder(decode_records(records), shape, rng)`: records carry 'im_file' (or JPEG bytes as 'image'), as the
+        reference's do before DecodeImage; every file of the batch goes through one decoder.decode() call (default: a
+        JpegDecoder the builder owns, checked decode) and stays on the device.  fallback: see decode_records."""
+        if decoder is None:
+            if self._decoder is None:
+                from .jpeg import JpegDecoder
+                self._decoder = JpegDecoder(device=self.device)
+            decoder = self._decoder
+        return self(decode_records(records, decoder, fallback, with_mixup=self.with_mixup), shape, rng)
+
+
+def _same_device(a, b):
+    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
+
+
+def source_image(im, device):
+    """What the builder makes of a record's image: a numpy uint8 [h,w,3] array (as given, or the one a CPU tensor wraps) is a
+    HOST source, packed into the blob; a uint8 [h,w,3] tensor on `device` with x-stride 3 and channel stride 1 is returned as
+    it is, an EXTERNAL source the kernels read in place.  Anything else raises: nothing is copied silently."""
+    if isinstance(im, torch.Tensor):
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise PPYoloHipError('expected a decoded uint8 image [h, w, 3], got %s %s' % (im.dtype, tuple(im.shape)))
+        if im.device.type == 'cpu':
+            return im.numpy()
+        if not _same_device(im.device, torch.device(device)):
+            raise PPYoloHipError('image tensor lives on %s, the builder on %s: move it there (`.to(device)`) or pass a numpy '
+                                 'array' % (im.device, device))
+        if im.stride(2) != 1 or im.stride(1) != 3 or (im.shape[0] > 1 and im.stride(0) < 3 * im.shape[1]):
+            raise PPYoloHipError('image tensor with strides %s: a device source needs channel stride 1, x-stride 3 and rows '
+                                 'that do not overlap (HWC; any row pitch); call `.contiguous()` on it first'
+                                 % (tuple(im.stride()),))
+        return im
+    if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+        raise PPYoloHipError('expected a decoded uint8 image [h, w, 3]')
+    return im
+
+
+def is_external(im):
+    """pack_batch's rule: a tensor that is not in host memory stays where it is."""
+    return isinstance(im, torch.Tensor) and im.device.type != 'cpu'
+
+
+def decode_records(records, decoder=None, fallback=None, with_mixup=True):
+    """The reference's DecodeImage.__call__ (tools/transform.py:79-128) for a whole batch, without the colour swap (the render
+    kernel's to_rgb does it): a record is decoded if it has no 'image' (its 'im_file' is read) or if its 'image' is bytes; so
+    is its 'mixup' record when with_mixup is set.  All of them go through ONE decoder.decode([bytes, ...]) call; 'image'
+    becomes the tensor it returns and 'h' / 'w' are set from it.  Records (and mixup records) are shallow copies: the
+    caller's list is not changed.
+
+    decoder: an object with decode(list of bytes) -> list of uint8 [h,w,3] BGR tensors, default JpegDecoder().  If it has
+    refusal(bytes) -> None | (kind, reason) (JpegDecoder: a header-only pass), the files it would refuse are found before
+    anything is decoded.  A file refused as 'unsupported' (progressive, ...) goes to fallback(bytes) -> uint8 BGR ndarray
+    and becomes a host source; without a fallback, and for a corrupt file always, PPYoloHipError names the record."""
+    if decoder is None:
+        from .jpeg import JpegDecoder
+        decoder = JpegDecoder()
+    out, pend = [], []          # pend: (record to fill, its name for messages, bytes)
+
+    def visit(rec, name):
+        rec = dict(rec)
+        im = rec.get('image')
+        if im is None or isinstance(im, (bytes, bytearray, memoryview)):
+            if im is None:
+                if not rec.get('im_file'):
+                    raise PPYoloHipError('%s has neither an image nor an im_file' % name)
+                name = '%s (%s)' % (name, rec['im_file'])
+                with open(rec['im_file'], 'rb') as fh:
+                    im = fh.read()
+            pend.append((rec, name, bytes(im)))
+        if with_mixup and rec.get('mixup') is not None:
+            rec['mixup'] = visit(rec['mixup'], name.split(' (')[0] + "['mixup']")
+        return rec
+
+    for i, rec in enumerate(records):
+        out.append(visit(rec, 'record %d' % i))
+
+    def done(rec, im):
+        rec['image'] = im
+        rec['h'], rec['w'] = int(im.shape[0]), int(im.shape[1])      # DecodeImage: set, or corrected from the decoded image
+
+    refusal = getattr(decoder, 'refusal', None)
+    good = []
+    for rec, name, data in pend:
+        r = refusal(data) if refusal is not None else None
+        if r is None:
+            good.append((rec, name, data))
+            continue
+        kind, reason = r
+        if kind != 'unsupported' or fallback is None:
+            raise PPYoloHipError('%s: %s JPEG: %s' % (name, kind, reason))
+        im = fallback(data)
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise PPYoloHipError('%s: the fallback must return a uint8 BGR array [h, w, 3]' % name)
+        done(rec, im)
+    if good:
+        try:
+            ims = decoder.decode([g[2] for g in good])
+        except PPYoloHipError as e:                 # 'item k: ...' of the decoder's list -> the record it came from
+            m = re.match(r'item (\d+): (.*)', str(e), re.S)
+            if m is None or int(m.group(1)) >= len(good):
+                raise
+            raise PPYoloHipError('%s: %s' % (good[int(m.group(1))][1], m.group(2))) from e
+        if len(ims) != len(good):
+            raise PPYoloHipError('the decoder returned %d images for %d files' % (len(ims), len(good)))
+        for (rec, _, _), im in zip(good, ims):
+            done(rec, im)
+    return out
 
 
 def _color_dtype(ops_):
@@ -538,9 +662,10 @@ def _color_dtype(ops_):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # The device blob: descriptors (struct AugSample of csrc/augment.hip, 8-byte fields first), tables, source pixels,
-# target element offsets / values, boxes.  Offsets are bytes from the start of the blob.
+# target element offsets / values, boxes.  Offsets are bytes from the start of the blob.  An EXTERNAL source (is_external)
+# puts no pixel into the blob: its descriptor field holds its index in layout['sources'] and the ext flag is set.
 
-DESC_I64 = 8            # src0, src1, xfirst, xw, yfirst, yw, (2 spare)
+DESC_I64 = 8            # src0, src1, xfirst, xw, yfirst, yw, ext0, ext1 (1: src is an index into the source table)
 DESC_F64 = 9 + 4        # hue matrix t; f32(factor), f32(1 - factor) of mixup; two spare
 DESC_I32 = 32
 DESC_BYTES = 8 * DESC_I64 + 8 * DESC_F64 + 4 * DESC_I32
@@ -550,9 +675,9 @@ def _desc(r, to_rgb, off):
     i64 = np.zeros(DESC_I64, np.int64)
     f64 = np.zeros(DESC_F64, np.float64)
     i32 = np.zeros(DESC_I32, np.int32)
-    i64[:6] = [off['src0'], off['src1'], off['xfirst'], off['xw'], off['yfirst'], off['yw']]
-    h0, w0 = r['image'].shape[:2]
-    h1, w1 = (r['mix_image'].shape[:2] if r['mix_image'] is not None else (0, 0))
+    i64[:] = [off['src0'], off['src1'], off['xfirst'], off['xw'], off['yfirst'], off['yw'], off['ext0'], off['ext1']]
+    h0, w0 = (int(v) for v in r['image'].shape[:2])
+    h1, w1 = ((int(v) for v in r['mix_image'].shape[:2]) if r['mix_image'] is not None else (0, 0))
     ops_ = r['ops']
     f32 = np.zeros(8, np.float32)
     codes = np.full(4, -1, np.int32)
@@ -579,7 +704,9 @@ DESC_BYTES += 32        # the eight float32 op constants (delta, 1 - delta) x 4
 
 
 def pack_batch(recipes, to_rgb, toff, tval, gt_bbox, gt_class, gt_score):
-    """-> (uint8 blob, layout dict of byte offsets).  Every part starts on a 16-byte boundary."""
+    """-> (uint8 blob, layout dict of byte offsets).  Every part starts on a 16-byte boundary.  layout['sources']: the
+    external sources in table order, the two of one sample next to each other (a tensor several samples use is listed once
+    per use); empty for recipes whose images are all host arrays, whose blob is what it always was."""
     parts, pos = [], [0]
 
     def put(b):
@@ -593,16 +720,27 @@ def pack_batch(recipes, to_rgb, toff, tval, gt_bbox, gt_class, gt_score):
         return o
 
     layout = dict(desc=put(b'\0' * (DESC_BYTES * len(recipes))))
-    descs = []
+    descs, sources = [], []
+
+    def source(im):             # -> (src, ext)
+        if is_external(im):
+            sources.append(im)
+            return len(sources) - 1, 1
+        if isinstance(im, torch.Tensor):
+            im = im.numpy()
+        return put(np.ascontiguousarray(im).tobytes()), 0
+
     for r in recipes:
-        off = dict(src0=put(np.ascontiguousarray(r['image']).tobytes()))
-        off['src1'] = put(np.ascontiguousarray(r['mix_image']).tobytes()) if r['mix_image'] is not None else 0
+        off = {}
+        off['src0'], off['ext0'] = source(r['image'])
+        off['src1'], off['ext1'] = source(r['mix_image']) if r['mix_image'] is not None else (0, 0)
         rp = r['resize']
         off['xfirst'] = put(rp['xfirst'].astype(np.int32).tobytes())
         off['xw'] = put(rp['xw'].astype(np.float32).tobytes())
         off['yfirst'] = put(rp['yfirst'].astype(np.int32).tobytes())
         off['yw'] = put(rp['yw'].astype(np.float32).tobytes())
         descs.append(_desc(r, to_rgb, off))
+    layout['sources'] = sources
     layout['toff'] = put(np.asarray(toff, np.int64).tobytes())
     layout['tval'] = put(np.asarray(tval, np.float32).tobytes())
     for k, a in (('gt_bbox', gt_bbox), ('gt_class', gt_class), ('gt_score', gt_score)):

@@ -10,6 +10,13 @@
 // canvas kernel  canvas_px of one sample into a caller buffer in its natural dtype (pinning only).
 // target kernels zero-fill of the dense targets, then the per-box elements the host computed (unique offsets).
 //
+// A source image lies either in the blob (src0 / src1 are byte offsets, rows packed) or OUTSIDE it (ext0 / ext1 set: src0 /
+// src1 are indices into a table of device images that arrives in the kernel arguments, each with its own row pitch and any
+// alignment -- a decoder's output or a cropped view of a larger tensor, read where it lies).  The table travels in windows of
+// AUG_MAX_SOURCES entries, one launch per window, consecutive windows sharing one entry; a sample is rendered by the
+// launch whose window starts at or below its lowest external index, so its two sources must lie in one window (adjacent
+// entries always do; pack_batch emits them so).  Samples without external sources belong to the first launch.
+//
 // numpy >= 2 (NEP 50) dtype chain, restated:
 //   mixup        f32(a) * f32(f), then + f32(b) * f32(1 - f) in float32 (0 where neither image lies), astype(uint8) truncates
 //   brightness   astype(f32); + f32(delta)          contrast  astype(f32); * f32(delta)
@@ -27,7 +34,8 @@ namespace {
 #pragma clang fp contract(off)
 
 struct AugSample {
-    long long src0, src1, xfirst, xw, yfirst, yw, spare0, spare1;       // byte offsets into the blob
+    long long src0, src1, xfirst, xw, yfirst, yw;                       // byte offsets into the blob
+    long long ext0, ext1;                                               // 1: src0 / src1 is an index into the source table
     double hue[9];                                                      // t of np.dot(img, t), row-major
     double spare[4];                                                    // [0], [1]: f32(factor), f32(1 - factor) of mixup
     int h0, w0, h1, w1, mh, mw, nops, eh, ew, ey, ex, fill[3], cy, cx, ch, cw, flip, color_dtype, canvas_dtype, mode,
@@ -45,16 +53,32 @@ struct NormArgs {
     int is_scale;
 };
 
+constexpr int AUG_MAX_SOURCES = 16;                     // table entries per launch
+constexpr int AUG_SRC_STEP = AUG_MAX_SOURCES - 1;       // distance of two windows' first entries
+struct AugSource {
+    const unsigned char *ptr;
+    long long pitch;                                    // bytes per row, >= 3 * w
+    int h, w;
+};
+struct AugSources {                                      // (the three ints first: a launch without external sources reads no further)
+    int base, count, last;                              // first table index of the window, entries in it, the last window
+    AugSource s[AUG_MAX_SOURCES];
+};
+// where a sample's two sources lie, resolved once per thread (source_px)
+struct AugPix {
+    const unsigned char *p0, *p1;
+    int pitch0, pitch1;                                 // (the entry point refuses a pitch beyond int)
+};
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // the ColorDistort output (colour-stage dtype) at (y, x) of the mixup / source image
-__device__ __forceinline__ void color_px(const unsigned char *blob, const AugSample &d, int y, int x, double v[3]) {
-    const unsigned char *s0 = blob + d.src0;
+__device__ __forceinline__ void color_px(const AugPix &sp, const AugSample &d, int y, int x, double v[3]) {
     float f[3];
     if (d.h1 > 0) {         // MixupImage._mixup_img
         const bool in0 = y < d.h0 && x < d.w0, in1 = y < d.h1 && x < d.w1;
-        const unsigned char *p0 = s0 + ((long long)clampi(y, 0, d.h0 - 1) * d.w0 + clampi(x, 0, d.w0 - 1)) * 3;
-        const unsigned char *p1 = blob + d.src1 + ((long long)clampi(y, 0, d.h1 - 1) * d.w1 + clampi(x, 0, d.w1 - 1)) * 3;
+        const unsigned char *p0 = sp.p0 + (long long)clampi(y, 0, d.h0 - 1) * sp.pitch0 + (long long)clampi(x, 0, d.w0 - 1) * 3;
+        const unsigned char *p1 = sp.p1 + (long long)clampi(y, 0, d.h1 - 1) * sp.pitch1 + (long long)clampi(x, 0, d.w1 - 1) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const int cs = d.to_rgb ? 2 - c : c;
@@ -64,7 +88,7 @@ __device__ __forceinline__ void color_px(const unsigned char *blob, const AugSam
             f[c] = (float)((int)m & 255);
         }
     } else {
-        const unsigned char *p0 = s0 + ((long long)clampi(y, 0, d.h0 - 1) * d.w0 + clampi(x, 0, d.w0 - 1)) * 3;
+        const unsigned char *p0 = sp.p0 + (long long)clampi(y, 0, d.h0 - 1) * sp.pitch0 + (long long)clampi(x, 0, d.w0 - 1) * 3;
 #pragma unroll
         for (int c = 0; c < 3; ++c) f[c] = (float)p0[d.to_rgb ? 2 - c : c];
     }
@@ -107,7 +131,7 @@ __device__ __forceinline__ void color_px(const unsigned char *blob, const AugSam
 }
 
 // the pre-resize canvas at (y, x): RandomFlipImage / RandomCrop index map, RandomExpand, colour stage
-__device__ __forceinline__ void canvas_px(const unsigned char *blob, const AugSample &d, int y, int x, double v[3]) {
+__device__ __forceinline__ void canvas_px(const AugPix &sp, const AugSample &d, int y, int x, double v[3]) {
     int X = (d.flip ? d.cw - 1 - x : x) + d.cx;
     int Y = y + d.cy;
     if (d.eh > 0) {
@@ -117,18 +141,17 @@ __device__ __forceinline__ void canvas_px(const unsigned char *blob, const AugSa
             for (int c = 0; c < 3; ++c) v[c] = (double)d.fill[c];
             return;
         }
-        color_px(blob, d, yy, xx, v);
+        color_px(sp, d, yy, xx, v);
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = (double)((long long)v[c] & 255);        // astype(uint8): truncate, wrap
         return;
     }
-    color_px(blob, d, Y, X, v);
+    color_px(sp, d, Y, X, v);
 }
 
 __device__ __forceinline__ bool desc_ok(const AugSample &d, long long nbytes, int S) {
     if (d.h0 <= 0 || d.w0 <= 0 || d.h1 < 0 || d.w1 < 0 || d.nops < 0 || d.nops > 4 || d.ch <= 0 || d.cw <= 0) return false;
-    if (d.src0 < 0 || d.src0 + (long long)d.h0 * d.w0 * 3 > nbytes) return false;
-    if (d.h1 > 0 && (d.src1 < 0 || d.src1 + (long long)d.h1 * d.w1 * 3 > nbytes)) return false;
+    if (d.w0 > 0x7fffffff / 3 || d.w1 > 0x7fffffff / 3) return false;           // a row's bytes fit an int (AugPix)
     if (d.mh < d.h0 || d.mw < d.w0 || d.mh < d.h1 || d.mw < d.w1) return false;
     const int H = d.eh > 0 ? d.eh : d.mh, W = d.eh > 0 ? d.ew : d.mw;
     if (d.cy < 0 || d.cx < 0 || d.cy + d.ch > H || d.cx + d.cw > W) return false;
@@ -141,6 +164,48 @@ __device__ __forceinline__ bool desc_ok(const AugSample &d, long long nbytes, in
     return true;
 }
 
+// One source of a sample: its first pixel and row pitch.  In the blob: the bytes must lie inside it.  External: the index must
+// lie in this launch's window and the table entry must have the descriptor's extent.
+__device__ __forceinline__ bool source_ok(const unsigned char *blob, long long nbytes, const AugSources &T, long long ext,
+                                          long long src, int h, int w, const unsigned char *&p, int &pitch) {
+    if (ext == 0) {
+        if (src < 0 || src + (long long)h * w * 3 > nbytes) return false;
+        p = blob + src;
+        pitch = 3 * w;
+        return true;
+    }
+    if (ext != 1 || src < T.base || src >= (long long)T.base + T.count) return false;
+    const AugSource &s = T.s[(int)(src - T.base)];
+    if (s.h != h || s.w != w) return false;
+    p = s.ptr;
+    pitch = (int)s.pitch;
+    return true;
+}
+
+// desc_ok's half about the sources, and whether the sample is THIS launch's: the launch whose window starts at or below the
+// sample's lowest external index (the first launch for a sample that has none) -> sp
+__device__ __forceinline__ bool source_px(const unsigned char *blob, long long nbytes, const AugSources &T, const AugSample &d,
+                                          AugPix &sp) {
+    if ((d.ext0 | d.ext1) == 0) {           // every source in the blob: the first launch's
+        if (T.base != 0 || d.src0 < 0 || d.src0 + (long long)d.h0 * d.w0 * 3 > nbytes) return false;
+        if (d.h1 > 0 && (d.src1 < 0 || d.src1 + (long long)d.h1 * d.w1 * 3 > nbytes)) return false;
+        sp.p0 = blob + d.src0;
+        sp.pitch0 = 3 * d.w0;
+        sp.p1 = blob + d.src1;
+        sp.pitch1 = 3 * d.w1;
+        return true;
+    }
+    const bool e0 = d.ext0 != 0, e1 = d.h1 > 0 && d.ext1 != 0;
+    long long lo = e0 ? d.src0 : (e1 ? d.src1 : 0);
+    if (e0 && e1 && d.src1 < lo) lo = d.src1;
+    if (lo < T.base || (!T.last && lo >= (long long)T.base + AUG_SRC_STEP)) return false;
+    if (!source_ok(blob, nbytes, T, d.ext0, d.src0, d.h0, d.w0, sp.p0, sp.pitch0)) return false;
+    sp.p1 = sp.p0;
+    sp.pitch1 = sp.pitch0;
+    if (d.h1 > 0 && !source_ok(blob, nbytes, T, d.ext1, d.src1, d.h1, d.w1, sp.p1, sp.pitch1)) return false;
+    return true;
+}
+
 __device__ __forceinline__ float normalise_f(float x, int c, const NormArgs &na) {
     if (na.is_scale) x = x / 255.0f;
     x = (float)((double)x - na.mean[c]);
@@ -149,15 +214,15 @@ __device__ __forceinline__ float normalise_f(float x, int c, const NormArgs &na)
 
 // one output pixel, all three channels, canvas dtype CT (0 u8, 1 f32, 2 f64)
 template <int CT>
-__device__ __forceinline__ void render_px(const unsigned char *blob, const AugSample &d, int dx, int dy, const float *lut,
-                                          const NormArgs &na, float out[3]) {
+__device__ __forceinline__ void render_px(const unsigned char *blob, const AugPix &sp, const AugSample &d, int dx, int dy,
+                                          const float *lut, const NormArgs &na, float out[3]) {
     typedef typename std::conditional<CT == F64, double, float>::type WT;
     const int *xf = reinterpret_cast<const int *>(blob + d.xfirst), *yf = reinterpret_cast<const int *>(blob + d.yfirst);
     const float *xw = reinterpret_cast<const float *>(blob + d.xw), *yw = reinterpret_cast<const float *>(blob + d.yw);
     double r[3];
     bool u8 = CT == U8;         // the resized value is a uint8 (table) rather than a float of the canvas type
     if (d.mode == MODE_NEAREST) {
-        canvas_px(blob, d, clampi(yf[dy], 0, d.ch - 1), clampi(xf[dx], 0, d.cw - 1), r);
+        canvas_px(sp, d, clampi(yf[dy], 0, d.ch - 1), clampi(xf[dx], 0, d.cw - 1), r);
     } else if (d.mode == MODE_AREA_FAST) {          // resizeAreaFast_: the block in row-major order
         const int x0 = xf[dx], y0 = yf[dy], area = d.ix * d.iy;
         if (CT == U8) {
@@ -165,7 +230,7 @@ __device__ __forceinline__ void render_px(const unsigned char *blob, const AugSa
             for (int yy = 0; yy < d.iy; ++yy)
                 for (int xx = 0; xx < d.ix; ++xx) {
                     double v[3];
-                    canvas_px(blob, d, clampi(y0 + yy, 0, d.ch - 1), clampi(x0 + xx, 0, d.cw - 1), v);
+                    canvas_px(sp, d, clampi(y0 + yy, 0, d.ch - 1), clampi(x0 + xx, 0, d.cw - 1), v);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) s[c] += (int)v[c];
                 }
@@ -181,7 +246,7 @@ __device__ __forceinline__ void render_px(const unsigned char *blob, const AugSa
             for (int yy = 0; yy < d.iy; ++yy)
                 for (int xx = 0; xx < d.ix; ++xx) {
                     double v[3];
-                    canvas_px(blob, d, clampi(y0 + yy, 0, d.ch - 1), clampi(x0 + xx, 0, d.cw - 1), v);
+                    canvas_px(sp, d, clampi(y0 + yy, 0, d.ch - 1), clampi(x0 + xx, 0, d.cw - 1), v);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) s[c] = s[c] + (WT)v[c];
                 }
@@ -197,7 +262,7 @@ __device__ __forceinline__ void render_px(const unsigned char *blob, const AugSa
             int hs[3] = {0, 0, 0};
             for (int j = 0; j < d.kx; ++j) {
                 double v[3];
-                canvas_px(blob, d, row, clampi(x0 + j, 0, d.cw - 1), v);
+                canvas_px(sp, d, row, clampi(x0 + j, 0, d.cw - 1), v);
                 const int wj = (int)xw[dx * d.kx + j];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) hs[c] += (int)v[c] * wj;
@@ -216,7 +281,7 @@ __device__ __forceinline__ void render_px(const unsigned char *blob, const AugSa
             WT hs[3] = {0, 0, 0};
             for (int j = 0; j < d.kx; ++j) {
                 double v[3];
-                canvas_px(blob, d, row, clampi(x0 + j, 0, d.cw - 1), v);
+                canvas_px(sp, d, row, clampi(x0 + j, 0, d.cw - 1), v);
                 const WT wj = (WT)xw[dx * d.kx + j];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
@@ -244,15 +309,16 @@ __device__ __forceinline__ void render_px(const unsigned char *blob, const AugSa
 }
 
 __global__ __launch_bounds__(256) void augment_render_kernel(const unsigned char *blob, long long nbytes, int S,
-                                                             const float *lut, NormArgs na, float *out) {
+                                                             const float *lut, NormArgs na, float *out, AugSources T) {
     const AugSample &d = reinterpret_cast<const AugSample *>(blob)[blockIdx.z];
     const int dx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int dy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (dx >= S || dy >= S || !desc_ok(d, nbytes, S)) return;
+    AugPix sp;
+    if (dx >= S || dy >= S || !desc_ok(d, nbytes, S) || !source_px(blob, nbytes, T, d, sp)) return;
     float o[3];
-    if (d.canvas_dtype == U8) render_px<U8>(blob, d, dx, dy, lut, na, o);
-    else if (d.canvas_dtype == F32) render_px<F32>(blob, d, dx, dy, lut, na, o);
-    else render_px<F64>(blob, d, dx, dy, lut, na, o);
+    if (d.canvas_dtype == U8) render_px<U8>(blob, sp, d, dx, dy, lut, na, o);
+    else if (d.canvas_dtype == F32) render_px<F32>(blob, sp, d, dx, dy, lut, na, o);
+    else render_px<F64>(blob, sp, d, dx, dy, lut, na, o);
     const long long plane = (long long)S * S;
     float *p = out + (long long)blockIdx.z * 3 * plane + (long long)dy * S + dx;
 #pragma unroll
@@ -260,13 +326,16 @@ __global__ __launch_bounds__(256) void augment_render_kernel(const unsigned char
 }
 
 __global__ __launch_bounds__(256) void augment_canvas_kernel(const unsigned char *blob, long long nbytes, int index, int h,
-                                                             int w, int dtype, void *out) {
+                                                             int w, int dtype, void *out, AugSources T) {
     const AugSample &d = reinterpret_cast<const AugSample *>(blob)[index];
     const int x = blockIdx.x * 64 + (threadIdx.x & 63);
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= w || y >= h || d.ch != h || d.cw != w || d.canvas_dtype != dtype || !desc_ok(d, nbytes, 0)) return;
+    AugPix sp;
+    if (x >= w || y >= h || d.ch != h || d.cw != w || d.canvas_dtype != dtype || !desc_ok(d, nbytes, 0) ||
+        !source_px(blob, nbytes, T, d, sp))
+        return;
     double v[3];
-    canvas_px(blob, d, y, x, v);
+    canvas_px(sp, d, y, x, v);
     const long long o = ((long long)y * w + x) * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -296,11 +365,38 @@ __global__ __launch_bounds__(256) void augment_scatter_kernel(float *out, long l
 
 }  // namespace
 
-extern "C" int ppy_augment_render_f32(const void *blob, long long blob_bytes, int n, int S, const float *lut,
-                                      const double *mean_std, int is_scale, float *out, void *stream) {
+// the source table of one launch: window k of the host arrays (consecutive windows share one entry)
+static int augment_window(int k, int windows, int n_src, const unsigned char *const *ptrs, const long long *pitch, const int *h,
+                          const int *w, AugSources &T) {
+    T.base = k * AUG_SRC_STEP;
+    T.count = n_src - T.base < AUG_MAX_SOURCES ? n_src - T.base : AUG_MAX_SOURCES;
+    T.last = k == windows - 1;
+    for (int i = 0; i < AUG_MAX_SOURCES; ++i) {
+        AugSource &s = T.s[i];
+        s.ptr = nullptr;
+        s.pitch = 0;
+        s.h = s.w = 0;
+        if (i >= T.count) continue;
+        const int g = T.base + i;
+        PPY_CHECK_ARG(ptrs[g] && h[g] > 0 && w[g] > 0 && pitch[g] >= 3LL * w[g] && pitch[g] <= 0x7fffffffLL);
+        s.ptr = ptrs[g];
+        s.pitch = pitch[g];
+        s.h = h[g];
+        s.w = w[g];
+    }
+    return PPY_OK;
+}
+
+static int augment_windows(int n_src) { return n_src <= AUG_MAX_SOURCES ? 1 : ceil_div(n_src - 1, AUG_SRC_STEP); }
+
+extern "C" int ppy_augment_render_src_f32(const void *blob, long long blob_bytes, int n, int S, const float *lut,
+                                          const double *mean_std, int is_scale, float *out, int n_src,
+                                          const unsigned char *const *src_ptrs, const long long *src_pitch, const int *src_h,
+                                          const int *src_w, void *stream) {
     ppy_drop_stale_error();
     PPY_CHECK_ARG(blob && lut && mean_std && out && n > 0 && n <= 65535 && S > 0 && S <= 8192 &&
                   blob_bytes >= (long long)n * (long long)sizeof(AugSample) && ((uintptr_t)blob & 7) == 0);
+    PPY_CHECK_ARG(n_src >= 0 && (n_src == 0 || (src_ptrs && src_pitch && src_h && src_w)));
     NormArgs na;
     for (int c = 0; c < 3; ++c) {
         na.mean[c] = mean_std[c];
@@ -308,19 +404,50 @@ extern "C" int ppy_augment_render_f32(const void *blob, long long blob_bytes, in
         PPY_CHECK_ARG(na.std[c] != 0.0);
     }
     na.is_scale = is_scale ? 1 : 0;
-    hipLaunchKernelGGL(augment_render_kernel, dim3(ceil_div(S, 64), ceil_div(S, 4), n), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned char *)blob, blob_bytes, S, lut, na, out);
+    const int windows = augment_windows(n_src);
+    AugSources T;
+    for (int k = 0; k < windows; ++k) {         // every entry is checked before the first launch
+        const int rc = augment_window(k, windows, n_src, src_ptrs, src_pitch, src_h, src_w, T);
+        if (rc != PPY_OK) return rc;
+    }
+    for (int k = 0; k < windows; ++k) {
+        augment_window(k, windows, n_src, src_ptrs, src_pitch, src_h, src_w, T);
+        hipLaunchKernelGGL(augment_render_kernel, dim3(ceil_div(S, 64), ceil_div(S, 4), n), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned char *)blob, blob_bytes, S, lut, na, out, T);
+    }
+    return ppy_launch_status();
+}
+
+extern "C" int ppy_augment_render_f32(const void *blob, long long blob_bytes, int n, int S, const float *lut,
+                                      const double *mean_std, int is_scale, float *out, void *stream) {
+    return ppy_augment_render_src_f32(blob, blob_bytes, n, S, lut, mean_std, is_scale, out, 0, nullptr, nullptr, nullptr, nullptr,
+                                      stream);
+}
+
+extern "C" int ppy_augment_canvas_src(const void *blob, long long blob_bytes, int index, int h, int w, int dtype, void *out,
+                                      int n_src, const unsigned char *const *src_ptrs, const long long *src_pitch,
+                                      const int *src_h, const int *src_w, void *stream) {
+    ppy_drop_stale_error();
+    PPY_CHECK_ARG(blob && out && index >= 0 && h > 0 && w > 0 && h <= 65535 * 4 && dtype >= 0 && dtype <= 2 &&
+                  blob_bytes >= (long long)(index + 1) * (long long)sizeof(AugSample) && ((uintptr_t)blob & 7) == 0);
+    PPY_CHECK_ARG(n_src >= 0 && (n_src == 0 || (src_ptrs && src_pitch && src_h && src_w)));
+    const int windows = augment_windows(n_src);
+    AugSources T;
+    for (int k = 0; k < windows; ++k) {
+        const int rc = augment_window(k, windows, n_src, src_ptrs, src_pitch, src_h, src_w, T);
+        if (rc != PPY_OK) return rc;
+    }
+    for (int k = 0; k < windows; ++k) {         // the sample is one window's: the other launches write nothing
+        augment_window(k, windows, n_src, src_ptrs, src_pitch, src_h, src_w, T);
+        hipLaunchKernelGGL(augment_canvas_kernel, dim3(ceil_div(w, 64), ceil_div(h, 4)), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned char *)blob, blob_bytes, index, h, w, dtype, out, T);
+    }
     return ppy_launch_status();
 }
 
 extern "C" int ppy_augment_canvas(const void *blob, long long blob_bytes, int index, int h, int w, int dtype, void *out,
                                   void *stream) {
-    ppy_drop_stale_error();
-    PPY_CHECK_ARG(blob && out && index >= 0 && h > 0 && w > 0 && h <= 65535 * 4 && dtype >= 0 && dtype <= 2 &&
-                  blob_bytes >= (long long)(index + 1) * (long long)sizeof(AugSample) && ((uintptr_t)blob & 7) == 0);
-    hipLaunchKernelGGL(augment_canvas_kernel, dim3(ceil_div(w, 64), ceil_div(h, 4)), dim3(256), 0, (hipStream_t)stream,
-                       (const unsigned char *)blob, blob_bytes, index, h, w, dtype, out);
-    return ppy_launch_status();
+    return ppy_augment_canvas_src(blob, blob_bytes, index, h, w, dtype, out, 0, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int ppy_augment_targets_f32(float *out, long long total, const long long *offsets, const float *values, int n,

@@ -113,6 +113,17 @@ class JpegDecoder(object):
             self._pool = ThreadPoolExecutor(max_workers=self.threads or MAX_THREADS, thread_name_prefix='ppy-jpeg')
         return list(self._pool.map(fn, range(n)))
 
+    def refusal(self, item):
+        """Header pass only, nothing is decoded: None if decode() would take the item as far as its markers tell, otherwise
+        (kind, reason) with kind 'unsupported' (progressive, arithmetic, ...: a file for another decoder) or 'corrupt'.
+        Damage inside the entropy data still surfaces in decode()."""
+        data = _bytes(item)
+        info = _lib.JpegInfo()
+        rc = lib().ppy_jpeg_info(data, len(data), ctypes.byref(info))
+        if rc == _lib.OK:
+            return None
+        return ('unsupported' if rc == -2 else 'corrupt'), info.reason.decode(errors='replace') or '?'
+
     def entropy_decode(self, items):
         """Host only: parse and Huffman-decode every item into a pinned staging buffer.  The returned HostBatch owns that buffer
         until reconstruct(hb) or release(hb); there are two buffers, so at most two batches can wait at a time (a third call

@@ -529,25 +529,46 @@ def preprocess_images(images_u8, target_size, lut, out, swap_rb=True):
         int(bool(swap_rb)), int(target_size), lut.data_ptr(), out.data_ptr(), _stream()), 'ppy_preprocess_u8_f32')
 
 
-def augment_render(blob, n, S, lut, mean, std, out, is_scale=True):
+def _augment_sources(blob, sources):
+    """The host arrays (n_src, ptrs, pitch, h, w) of ppy_augment_*_src for a list of uint8 [h,w,3] device tensors: pixel stride 3,
+    any row pitch >= 3 * w, any alignment (a view `big[3:3+h, 5:5+w]` is a source as it lies)."""
+    n = len(sources)
+    for im in sources:
+        assert isinstance(im, torch.Tensor) and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3
+        assert im.stride(2) == 1 and im.stride(1) == 3 and im.device == blob.device
+        assert im.shape[0] > 0 and im.shape[1] > 0 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])
+    return (n, (ctypes.c_void_p * n)(*[im.data_ptr() for im in sources]),
+            (ctypes.c_longlong * n)(*[max(im.stride(0), 3 * im.shape[1]) for im in sources]),
+            (ctypes.c_int * n)(*[im.shape[0] for im in sources]), (ctypes.c_int * n)(*[im.shape[1] for im in sources]))
+
+
+def augment_render(blob, n, S, lut, mean, std, out, is_scale=True, sources=None):
     """TrainBatchBuilder's render launch: blob = device uint8 copy of augment.pack_batch (descriptors at offset 0) ->
-    out [n,3,S,S] float32."""
+    out [n,3,S,S] float32.  sources: the device images the blob's descriptors name by index (pack_batch's layout['sources'])."""
     _dev(blob, lut, out)
     assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.data_ptr() % 8 == 0
     assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, S, S)
     assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (3, 256)
     ms = (ctypes.c_double * 6)(*[float(v) for v in list(mean) + list(std)])
-    check(lib().ppy_augment_render_f32(blob.data_ptr(), blob.numel(), int(n), int(S), lut.data_ptr(), ms, int(bool(is_scale)),
-                                       out.data_ptr(), _stream()), 'ppy_augment_render_f32')
+    if not sources:
+        check(lib().ppy_augment_render_f32(blob.data_ptr(), blob.numel(), int(n), int(S), lut.data_ptr(), ms, int(bool(is_scale)),
+                                           out.data_ptr(), _stream()), 'ppy_augment_render_f32')
+        return
+    check(lib().ppy_augment_render_src_f32(blob.data_ptr(), blob.numel(), int(n), int(S), lut.data_ptr(), ms, int(bool(is_scale)),
+                                           out.data_ptr(), *_augment_sources(blob, sources), _stream()), 'ppy_augment_render_src_f32')
 
 
-def augment_canvas(blob, index, out):
+def augment_canvas(blob, index, out, sources=None):
     """The pre-resize image of sample `index` of a packed blob -> out [h,w,3] uint8 / float32 / float64 (its canvas dtype)."""
     _dev(blob, out)
     assert blob.dtype == torch.uint8 and blob.is_contiguous() and out.is_contiguous() and out.dim() == 3 and out.shape[2] == 3
     dt = {torch.uint8: 0, torch.float32: 1, torch.float64: 2}[out.dtype]
-    check(lib().ppy_augment_canvas(blob.data_ptr(), blob.numel(), int(index), out.shape[0], out.shape[1], dt, out.data_ptr(),
-                                   _stream()), 'ppy_augment_canvas')
+    if not sources:
+        check(lib().ppy_augment_canvas(blob.data_ptr(), blob.numel(), int(index), out.shape[0], out.shape[1], dt, out.data_ptr(),
+                                       _stream()), 'ppy_augment_canvas')
+        return
+    check(lib().ppy_augment_canvas_src(blob.data_ptr(), blob.numel(), int(index), out.shape[0], out.shape[1], dt, out.data_ptr(),
+                                       *_augment_sources(blob, sources), _stream()), 'ppy_augment_canvas_src')
 
 
 def augment_targets(flat, blob, off_pos, val_pos, n):
