@@ -588,6 +588,29 @@ int ppy_nms_candidates_f32(const float *scores, int N, int M, int C, float score
                            uint32_t *cand_key, uint32_t *cand_idx, int *cand_count, int cand_cap,
                            void *stream);
 
+/* multiclass_nms (PaddleDetection's operator of that name: greedy per-class hard NMS) for a batch, from the same
+ * candidate lists as ppy_matrix_nms_f32 (cand_key / cand_idx = box * C + class / cand_count, in any order).
+ * Per class != background_label: the candidates by (score descending, box index ascending), the first nms_top_k of
+ * them, then a greedy scan that selects a candidate iff iou <= nms_threshold holds against every box already selected
+ * in that class (a NaN IoU suppresses).  iou is JaccardOverlap in fp32, one rounding per operation:
+ * 0 if the boxes are disjoint, else iw * ih / ((area_a + area_b) - iw * ih) with iw = (min x2 - max x1) + norm,
+ * norm = 0 if normalized else 1, area = 0 for an inverted box.  Across classes: the keep_top_k highest scores (ties to
+ * the lower class, then the lower box index), emitted in (class ascending, score descending, box ascending) order.
+ * Outputs as ppy_matrix_nms_f32 writes them: out_dets [N][keep_top_k][6] = (label, score, x0,y0,x1,y1), rows >=
+ * out_count[n] are -1; out_keep_idx [N][keep_top_k] = box * C + class (-1 padding).  The score is the original one.
+ * Limits (PPY_ERR_UNSUPPORTED outside, nothing is clamped): 1 <= nms_top_k <= 1024, 1 <= keep_top_k <= 1024,
+ * nms_eta == 1 (no adaptive threshold); Paddle's -1 = "no limit" is therefore not accepted.
+ * ws: ppy_multiclass_nms_workspace_bytes(N, num_classes, nms_top_k, cand_cap) bytes, 16-byte aligned
+ * (= 16-byte-rounded 4 N + 8 N num_classes nms_top_k: the selections of every class before the keep_top_k cut; the
+ * candidate list itself is filtered in place, so the bound does not depend on cand_cap).  No host synchronisation:
+ * three launches on `stream` (csrc/multiclass_nms.hip), capturable into a graph. */
+size_t ppy_multiclass_nms_workspace_bytes(int N, int num_classes, int nms_top_k, int cand_cap);
+int ppy_multiclass_nms_f32(const float *boxes, int M_total, int num_classes, const uint32_t *cand_key,
+                           const uint32_t *cand_idx, const int *cand_count, int cand_cap, int N,
+                           int nms_top_k, int keep_top_k, float nms_threshold, int normalized, float nms_eta,
+                           int background_label, float *out_dets, int *out_count, int *out_keep_idx,
+                           void *ws, size_t ws_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * conv2 -> conv3 of an identity bottleneck in ONE launch (round 5; reference model/resnet_vd.py:81-87:
  * relu(bn3(conv3(relu(bn2(conv2(t))))) + x)): conv A = 3x3 / stride 1 / pad 1, CA -> KA, BatchNorm, ReLU; conv B = 1x1, KA -> KB,

@@ -17,6 +17,15 @@ def _matrix_nms_defaults():
                 nms_top_k=500, keep_top_k=100, use_gaussian=False, gaussian_sigma=2.)
 
 
+def multiclass_nms_defaults():
+    """`cfg.nms_cfg = multiclass_nms_defaults()` switches a configuration to greedy per-class hard NMS
+    (model/multiclass_nms.py).  The reference ships no such settings and PaddleDetection's configuration files were not
+    at hand when this was written: these values were CHOSEN HERE (the usual YOLOv3-style ones, pixel coordinates), they
+    are not copied from a published configuration -- set the keys of the model you reproduce."""
+    return dict(nms_type='multiclass_nms', score_threshold=0.01, nms_top_k=1000, keep_top_k=100, nms_threshold=0.45,
+                normalized=False, background_label=-1)
+
+
 def _train_transforms(cfg, gt2yolo):
     """The reference's training-reader settings (config/ppyolo_2x.py:154-251; ppyolo_r18vd.py differs in
     gt2YoloTarget only), consumed by ppyolo_hip.augment.TrainBatchBuilder.  `context` is left as the

@@ -5,8 +5,9 @@ Same class names, constructor arguments and `state_dict` keys as the reference's
 reference's exact entries -- including the parameter-less CoordConv / SPP / DropBlock
 placeholders -- because their positions are what the checkpoint keys
 (`head.detection_blocks.{i}.layers.{k}.*`) encode.  Execution is by plan emission
-(ppyolo_hip/engine.py); decode + Matrix-NMS parameters are handed to the executor, which
-runs ppy_yolo_decode_f32 / ppy_matrix_nms_f32 (reference :21-141, :424-469).
+(ppyolo_hip/engine.py); decode + NMS parameters are handed to the executor, which runs
+ppy_yolo_decode_f32 and ppy_matrix_nms_f32 or ppy_multiclass_nms_f32, as nms_cfg['nms_type'] says
+(reference :21-141, :424-469).
 """
 import copy
 
@@ -14,6 +15,14 @@ import numpy as np
 import torch
 
 from model.custom_layers import Conv2dUnit, CoordConv, SPP, DropBlock, get_norm
+
+# nms_cfg keys per nms_type: (required, {optional: default}).  matrix_nms: reference model/matrix_nms.py:102-103;
+# multiclass_nms: PaddleDetection's operator of that name as model/multiclass_nms.py runs it (nms_eta must stay 1.0).
+_NMS_KEYS = {
+    'matrix_nms': (('score_threshold', 'post_threshold', 'nms_top_k', 'keep_top_k'), dict(use_gaussian=False, gaussian_sigma=2.)),
+    'multiclass_nms': (('score_threshold', 'nms_top_k', 'keep_top_k', 'nms_threshold', 'normalized', 'background_label'),
+                       dict(nms_eta=1.0)),
+}
 
 
 class DetectionBlock(torch.nn.Module):
@@ -180,8 +189,22 @@ class YOLOv3Head(torch.nn.Module):
         if nms is None:
             raise ValueError('YOLOv3Head needs nms_cfg for inference (reference demo.py:87)')
         nms_type = nms.pop('nms_type')
-        if nms_type != 'matrix_nms':
-            raise NotImplementedError('only matrix_nms (the reference disables multiclass_nms, head.py:465-468)')
+        if nms_type not in _NMS_KEYS:      # (the reference reads nms_type and leaves its multiclass_nms branch commented out, head.py:459-468)
+            raise NotImplementedError('nms_type %r: supported are %s' % (nms_type, ', '.join(sorted(_NMS_KEYS))))
+        required, optional = _NMS_KEYS[nms_type]
+        unknown = sorted(set(nms) - set(required) - set(optional))
+        missing = sorted(set(required) - set(nms))
+        if unknown or missing:
+            raise ValueError('nms_cfg for %s: %s' % (nms_type, '; '.join(
+                ['unknown key(s) %s' % ', '.join(unknown)] * bool(unknown) + ['missing key(s) %s' % ', '.join(missing)] * bool(missing))))
+        for k, v in optional.items():
+            nms.setdefault(k, v)
+        if nms_type == 'multiclass_nms':      # the kernels' range (ppy_multiclass_nms_f32); Paddle's -1 = "no limit" is not accepted
+            for k in ('nms_top_k', 'keep_top_k'):
+                if not 1 <= int(nms[k]) <= 1024:
+                    raise ValueError('nms_cfg for multiclass_nms: %s=%r is outside the supported 1..1024' % (k, nms[k]))
+            if float(nms['nms_eta']) != 1.0:
+                raise ValueError('nms_cfg for multiclass_nms: nms_eta=%r (only 1.0: no adaptive threshold)' % (nms['nms_eta'],))
         levels = []
         for i, o in enumerate(outs):
             assert o.H == o.W, 'yolo_box assumes square feature maps (reference head.py:25-27)'
@@ -189,7 +212,7 @@ class YOLOv3Head(torch.nn.Module):
                                downsample=int(self.downsample[i])))
         M = sum(o.H * o.W * len(self.anchor_masks[i]) for i, o in enumerate(outs))
         return dict(levels=levels, num_classes=self.num_classes, scale_x_y=self.scale_x_y, iou_aware=self.iou_aware,
-                    iou_aware_factor=self.iou_aware_factor, clip_bbox=self.clip_bbox, M_total=M, nms=nms)
+                    iou_aware_factor=self.iou_aware_factor, clip_bbox=self.clip_bbox, M_total=M, nms=nms, nms_type=nms_type)
 
     def add_param_group(self, param_groups, base_lr, base_wd):      # reference model/head.py:366-373
         for blk in self.detection_blocks:

@@ -278,7 +278,10 @@ class HipExecutor(object):
             self.out_dets = torch.zeros((p.N, kk, 6), dtype=torch.float32, device=self.device)
             self.out_count = torch.zeros((p.N,), dtype=torch.int32, device=self.device)
             self.out_keep = torch.zeros((p.N, kk), dtype=torch.int32, device=self.device)
-            self.nms_ws = K.matrix_nms_workspace(p.N, self.device)
+            if d.get('nms_type', 'matrix_nms') == 'multiclass_nms':
+                self.nms_ws = K.multiclass_nms_workspace(p.N, C, d['nms']['nms_top_k'], cap, self.device)
+            else:
+                self.nms_ws = K.matrix_nms_workspace(p.N, self.device)
         self.math = math_mode()
         placeholders = any(op.get('w') is not None and op['w'].is_meta for op in p.setup_ops + p.ops)
         if share is not None and share.math == self.math and len(share.plan.ops) == len(p.ops) \
@@ -558,6 +561,11 @@ class HipExecutor(object):
                              d['iou_aware_factor'], d['clip_bbox'], self.im_size, self.boxes,
                              d['nms']['score_threshold'], self.cand_key, self.cand_idx, self.cand_count)
         n = d['nms']
+        if d.get('nms_type', 'matrix_nms') == 'multiclass_nms':
+            K.multiclass_nms(self.boxes, d['num_classes'], self.cand_key, self.cand_idx, self.cand_count, n['nms_top_k'],
+                             n['keep_top_k'], n['nms_threshold'], n['normalized'], n['nms_eta'], n['background_label'],
+                             self.out_dets, self.out_count, self.out_keep, self.nms_ws)
+            return
         K.matrix_nms(self.boxes, d['num_classes'], self.cand_key, self.cand_idx, self.cand_count,
                      n['post_threshold'], n['nms_top_k'], n['keep_top_k'], n['use_gaussian'], n['gaussian_sigma'],
                      self.out_dets, self.out_count, self.out_keep, self.nms_ws)

@@ -722,3 +722,32 @@ def matrix_nms(boxes, num_classes, cand_key, cand_idx, cand_count, post_threshol
                                    out_dets.data_ptr(), out_count.data_ptr(), out_keep.data_ptr(), ws.data_ptr(),
                                    ws.numel() * ws.element_size(), _stream()),
           'ppy_matrix_nms_f32')
+
+
+def multiclass_nms_workspace(N, num_classes, nms_top_k, cand_cap, device):
+    """Scratch tensor for multiclass_nms on a batch of N images (the bound depends on N, num_classes and nms_top_k; it is
+    0 bytes -- an empty tensor, which the call then refuses -- for an nms_top_k outside 1..1024)."""
+    nbytes = int(lib().ppy_multiclass_nms_workspace_bytes(int(N), int(num_classes), int(nms_top_k), int(cand_cap)))
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+
+
+def multiclass_nms(boxes, num_classes, cand_key, cand_idx, cand_count, nms_top_k, keep_top_k, nms_threshold, normalized,
+                   nms_eta, background_label, out_dets, out_count, out_keep, ws=None):
+    """Greedy per-class hard NMS (PaddleDetection's multiclass_nms) on the candidate lists of a batch; outputs as matrix_nms
+    writes them.  Supported: 1 <= nms_top_k <= 1024, 1 <= keep_top_k <= 1024, nms_eta == 1 (Paddle's -1 = "no limit" is not
+    accepted); anything else raises PPYoloHipError naming the parameter."""
+    _dev(boxes, cand_key, cand_idx, cand_count, out_dets, out_count, out_keep)
+    N, M, _ = boxes.shape
+    if ws is None:
+        ws = multiclass_nms_workspace(N, num_classes, nms_top_k, cand_key.shape[1], boxes.device)
+    rc = lib().ppy_multiclass_nms_f32(boxes.data_ptr(), M, int(num_classes), cand_key.data_ptr(), cand_idx.data_ptr(),
+                                      cand_count.data_ptr(), cand_key.shape[1], N, int(nms_top_k), int(keep_top_k),
+                                      float(nms_threshold), int(bool(normalized)), float(nms_eta), int(background_label),
+                                      out_dets.data_ptr(), out_count.data_ptr(), out_keep.data_ptr(), ws.data_ptr(),
+                                      ws.numel() * ws.element_size(), _stream())
+    if rc == -2:          # PPY_ERR_UNSUPPORTED: say which parameter left the supported range
+        bad = [('nms_top_k=%r (supported: 1..1024)' % (nms_top_k,), not 1 <= int(nms_top_k) <= 1024),
+               ('keep_top_k=%r (supported: 1..1024)' % (keep_top_k,), not 1 <= int(keep_top_k) <= 1024),
+               ('nms_eta=%r (supported: 1.0, no adaptive threshold)' % (nms_eta,), float(nms_eta) != 1.0)]
+        raise _lib.PPYoloHipError('ppy_multiclass_nms_f32: unsupported ' + ', '.join(t for t, b in bad if b))
+    check(rc, 'ppy_multiclass_nms_f32')
