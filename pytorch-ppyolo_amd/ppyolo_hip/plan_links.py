@@ -6,6 +6,7 @@ chose; sync_plan over the final state.  Whatever changes a tile id afterwards re
 op_io(op) is what an op reads and writes UNDER the links made so far and a BufferIndex a snapshot of it: whoever makes links
 builds a new one before the next rule reads it.  A `cfg id -> ConvCfg` lookup is handed in (ops.conv_cfg; a table in a test)."""
 from ._lib import PPYoloHipError
+from .train_plan import shape_key
 
 
 def has_f16(op):
@@ -23,9 +24,8 @@ def tune_key(op, with_g=True):
     # ':p': the layer also owns the 2x2 average of its output (link_pools)
     # ':g': the layer's input can arrive pre-split from its one producer (split_pairs marks 'gp_in'): its main loop has
     # no split work, another tile may win -- such entries are measured in that form; without one the plain entry is used
-    return '%s:N%d:H%d:W%d:C%d:K%d:R%d:s%d%s%s%s' % ('dcnf' if op['op'] == 'dcn' else op['op'], x.N, x.H, x.W, C, Kout, R,
-                                                     op['stride'], ':f' if has_f16(op) else '', ':p' if op.get('pool') is not None else '',
-                                                     ':g' if (op.get('gp_in') and with_g) else '')
+    return shape_key('dcnf' if op['op'] == 'dcn' else op['op'], x.N, x.H, x.W, C, Kout, R, op['stride'], has_f16(op),
+                     op.get('pool') is not None, bool(op.get('gp_in') and with_g))
 
 
 def apply_tuned(ops, tab, tab_x3):

@@ -16,6 +16,7 @@ gt_score, targets)`, `all_loss.backward()`, `optimizer.step()` -- as a sequence 
 The convolutions run on the exact bf16x3 split (no tracked maxima needed); torch supplies memory, streams and
 `torch.distributed` only.  There is no CPU path.
 """
+import functools
 import json
 import os
 
@@ -24,6 +25,7 @@ import warnings
 import torch
 
 from . import ops as K
+from . import train_plan as TP
 from ._lib import PPYoloHipError, conv_cfg, conv_cfgs
 
 TRAIN_TABLE = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuned_gfx950_train.json')
@@ -62,31 +64,31 @@ class Act(object):
         return self.t[..., self.coff:self.coff + self.C].permute(0, 3, 1, 2).contiguous()
 
 
-def _r32(c):
-    return (c + 31) // 32 * 32
-
-
-def train_fwd_cfg(cfg_id, splitk):
-    """(tile configuration, split-K) a table names for a forward convolution -> the pair the training forward launches.  The
-    training tables fall back on the inference tables' entries, whose ids include families that cannot give the BatchNorm
-    statistics this forward takes from the epilogue:
-      * a k-parity tile (round 6): the same tile with one consumer group (its stats_twin), split-K kept;
-      * a wave-private small-output tile: its split-K counts k-parts inside the workgroup, not workspace splits, and it writes no
-        statistics -- the library's own choice instead, (-1, 0).
-    Data gradients keep the table's ids: they take no statistics, and every family runs them (tests/test_gpu_train_replay.py)."""
-    d = conv_cfg(cfg_id) if cfg_id >= 0 else None
-    if d is not None and d.family == 'kparity':
-        return d.stats_twin, splitk
-    if d is not None and d.splitk_mode == 'workgroup':
-        return -1, 0
-    return cfg_id, splitk
+train_fwd_cfg = functools.partial(TP.train_fwd_cfg, cfg_of=conv_cfg)      # (cfg id, split-K) of a table -> what the forward launches
 
 
 def tune_cfgs(f16):
-    """The tile configurations a training forward is measured on: the nine bf16x3 tiles; with the f16x2 operands the f16x2 tiles x
-    {2, 3, 4} LDS stages and the specialised-wave tiles that emit the BatchNorm statistics it takes from the epilogue (no k-parity tile)."""
-    fams = ('f16x2', 'ws', 'ws_pre') if f16 else ('bf16x3',)
-    return [d.id for d in conv_cfgs() if d.family in fams and d.bn_stats == f16]
+    return TP.tune_cfgs(f16, conv_cfgs())
+
+
+class Pass(object):
+    """What belongs to ONE forward (+ backward) pass.  TrainStep.cur is the pass in progress; a prefetched backbone runs under a
+    pass of its own (prefetch_backbone), so whatever is per pass goes here and nowhere else."""
+    __slots__ = ('ws', 'bn_part', 'amax_arena', 'amax_next', 'nbt', 'flops', 'tape', 'coord_slot')
+
+    def __init__(self, ws, coord_slot, bn_part=None, amax_arena=None):
+        self.ws = ws                        # conv split-K / dgrad / wgrad / reductions
+        self.bn_part = bn_part              # BatchNorm partials from the convolutions' epilogues (grown on demand)
+        self.amax_arena, self.amax_next = amax_arena, 0      # tracked-maximum slots: one arena, zeroed once per pass, and its cursor
+        self.nbt = []                       # keys of the BatchNorm step counters touched by this forward (bumped in one launch)
+        self.flops = 0                      # algorithmic convolution FLOPs (2 * MAC) of the forward + backward
+        self.tape = []                      # the backward, recorded by the forward
+        self.coord_slot = coord_slot        # which of a layer's coordinate-ready buffers new_coord hands out (0 / 1: prefetched backbones)
+
+    def zero_amax(self):
+        if self.amax_arena is not None:
+            self.amax_arena.zero_()
+        self.amax_next = 0
 
 
 class ModelSettings(object):
@@ -139,7 +141,7 @@ class TrainStep(object):
         self.model, self.cfg, self.dev, self.world = model, cfg, dev, world_size
         self.external = bool(external_optimizer)
         self.sd = model.state_dict()                       # tensors alias the module's parameters / buffers
-        want = [k for k, _ in model.named_parameters() if self._stage_of(k) > self.freeze_at]
+        want = [k for k, _ in model.named_parameters() if TP.stage_of(k) > self.freeze_at]
         if self.external:
             got = [k for k, q in model.named_parameters() if q.requires_grad]
             if got != want:
@@ -152,25 +154,16 @@ class TrainStep(object):
         self._const = {}
         self._coord_bufs = {}
         self._prep, self._prep_done = None, False      # ops.WeightPrepTable of the trainable convolutions (built after the first step)
-        self.ws = torch.empty(96 << 20, dtype=torch.float32, device=dev)     # conv split-K / dgrad / wgrad / reductions
-        # The weight gradient of a head convolution has no consumer before the optimizer: it runs on a SECOND stream beside the data
-        # gradient chain (its own workspace; the operands are kept alive until the join at the end of the backward).  Same kernels,
-        # same results bit for bit; PPYOLO_HIP_TRAIN_WGRAD_STREAM=0 puts it back in line.
-        self._wgrad_side = os.environ.get('PPYOLO_HIP_TRAIN_WGRAD_STREAM', '1') == '1'
-        # frozen 1x1 layers on the streaming kernel: BatchNorm from the convolution's own epilogue, no raw tensor (conv_unit)
-        # (PPYOLO_HIP_TRAIN_BN_EPILOGUE: 0 = off, 1 = the layers the table puts on the streaming kernel, 2 (default) = those and every
-        # frozen C = 128 1x1 layer the kernel accepts, whatever tile the table names: 11.82 -> 11.58 -> 11.48 ms on the R50vd-608 step)
-        self.bn_epilogue = os.environ.get('PPYOLO_HIP_TRAIN_BN_EPILOGUE', '2') in ('1', '2')
-        self.bn_epilogue_all = os.environ.get('PPYOLO_HIP_TRAIN_BN_EPILOGUE', '2') == '2'
+        self.cur = Pass(torch.empty(96 << 20, dtype=torch.float32, device=dev), 2)      # (coordinate slot 2: the plain loop)
+        nccl = world_size > 1 and torch.distributed.is_available() and torch.distributed.is_initialized() \
+            and torch.distributed.get_backend() == 'nccl'
+        # every PPYOLO_HIP_TRAIN_* switch read here, resolved in one place: train_plan.switches says what each one buys
+        (self._wgrad_side, self._async_tail, self.bn_epilogue, self.bn_epilogue_all, self.f16, self.fp32, self.overlap, self.fuse_stats,
+         self._prefetch_on) = TP.switches(os.environ, world_size, nccl, self.external)
         self._wstream = torch.cuda.Stream(device=dev) if self._wgrad_side else None
         self._ws_side = None
         self._wkeep = []
         self._wpending = False
-        # ... and so do the optimizer step, the EMA update and the re-split of the updated weights (sgd, _prepare_weights): the next
-        # step's frozen layers do not read a trainable parameter, so its forward starts while they run; the first use of a trainable
-        # parameter (weight() / param()) or a reader outside the step (sync_to_model, grads) waits for them (_await_params).
-        # PPYOLO_HIP_TRAIN_ASYNC_TAIL=0: in line.
-        self._async_tail = self._wgrad_side and os.environ.get('PPYOLO_HIP_TRAIN_ASYNC_TAIL', '1') == '1'
         self._params_pending = False
         self.steps_done = 0
         self.momentum = cfg.optimizerBuilder['optimizer']['momentum']
@@ -188,7 +181,6 @@ class TrainStep(object):
             torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0)
         self.seed_base = (int(os.environ.get('PPYOLO_HIP_SEED', '0')) * 0x2545F491 + rank * 0x5851F42D) & 0xFFFFFFFFFFFF
         self.acts = None
-        self.flops = 0                      # algorithmic convolution FLOPs (2 * MAC) of the last forward + backward
         # tile configurations: the measured bf16x3 table of the inference path knows the backbone's shapes; the head's own
         # (CoordConv channels padded to 32, the data gradients' transposed geometries) are in tuned_gfx950_train.json,
         # written by autotune() below.  Keys are the geometry the forward kernel sees.
@@ -197,51 +189,21 @@ class TrainStep(object):
         if os.path.exists(TRAIN_TABLE):
             with open(TRAIN_TABLE) as fh:
                 self._tuned.update(json.load(fh))
-        # forward convolutions on the f16x2 kernels (3 MFMA products instead of 6) where the input's maximum is tracked -- by
-        # bn_train_apply for every normalised activation, propagated through concatenations / pooling / DropBlock here;
-        # PPYOLO_HIP_TRAIN_MATH=bf16x3 keeps every convolution on the exact bf16 split
-        self.f16 = os.environ.get('PPYOLO_HIP_TRAIN_MATH', 'f16x2') == 'f16x2'
-        # PPYOLO_HIP_TRAIN_MATH=fp32 (bench.py's value_fp32_exact leg; with PPY_WGRAD_FP32=1 and PPY_DGRAD_FP32=1 in the environment of
-        # the process): every convolution, data gradient and weight gradient on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32)
-        self.fp32 = os.environ.get('PPYOLO_HIP_TRAIN_MATH', 'f16x2') == 'fp32'
         self._tuned_f = dict(tuned_table('f16x2')) if self.f16 else {}
         if self.f16 and os.path.exists(TRAIN_TABLE_F16):
             with open(TRAIN_TABLE_F16) as fh:
                 self._tuned_f.update(json.load(fh))
-        self._amax_arena, self._amax_next = None, 0
-        # Gradient buckets go out as asynchronous all-reduces DURING the backward.  With backend nccl (= RCCL) that puts RCCL's fp32
-        # sum kernels beside this library's 16-bit-MFMA kernels on the same CUs -- the co-residence under which a packed-fp32
-        # instruction form misreads.  librccl's gfx950 code holds 945 v_pk_*_f32, none in that form
-        # (tools/rccl_pk_scan.py -> profiles/r03_rccl_pk_scan.txt), but the pair has never executed on hardware (no multi-GPU
-        # box): under nccl the overlap is therefore OPT-IN (PPYOLO_HIP_TRAIN_OVERLAP=1) and the default is one collective after
-        # the backward, when no MFMA kernel of this rank is in flight; other backends (gloo: host reductions) overlap by default.
-        ov = os.environ.get('PPYOLO_HIP_TRAIN_OVERLAP')
-        nccl = world_size > 1 and torch.distributed.is_available() and torch.distributed.is_initialized() \
-            and torch.distributed.get_backend() == 'nccl'
-        self.overlap = ((ov == '1') if nccl else (ov != '0')) and not self.external
         self._buckets, self._pending, self._works, self._reduced = None, {}, [], []
         self.tune = False                   # True: measure shapes the tables do not know while stepping (autotune())
-        self.fuse_stats = os.environ.get('PPYOLO_HIP_TRAIN_FUSE_STATS', '1') == '1'      # BatchNorm statistics from the conv epilogue
-        self._bn_part = None
         self._measured = {}
-        self._nbt = []                      # keys of the BatchNorm step counters touched by this forward (bumped in one launch)
         self._nbt_flat, self._nbt_keys = None, None
-        # Round 5: with the whole backbone frozen (freeze_at = 5, the reference's configurations) its training-mode forward reads no
-        # trainable parameter, so the NEXT batch's backbone can run on a third stream beside THIS batch's head forward / loss /
-        # backward (prefetch_backbone, step(..., next_x=...)): same kernels on the same inputs in the same order per tensor --
-        # bit-identical losses, gradients and running statistics -- with its own workspace, BatchNorm partials and (two alternating)
-        # blocks of tracked-maximum slots.  PPYOLO_HIP_TRAIN_PREFETCH=0 ignores next_x.
-        self._prefetch_on = os.environ.get('PPYOLO_HIP_TRAIN_PREFETCH', '1') == '1'
         self._bstream = None
         self._pref = None
         self._own_backbone_done = None
-        self._coord_slot = 2                # which of a layer's coordinate-ready buffers new_coord hands out (0 / 1: prefetched backbones)
-        self._b_res = None                  # [ws, bn_part, [arena0, arena1], which]
+        self._stream0 = K.stream_first_cfg()
+        self._b_res = None                  # what the prefetched backbones' passes run on: [ws, bn_part, [arena0, arena1], which]
 
-    @staticmethod
-    def _stage_of(key):
-        """Backbone stage (1..5) a state_dict key belongs to; 6 = the head."""
-        return int(key[len('backbone.stage')]) if key.startswith('backbone.stage') else 6
+    flops = property(lambda self: self.cur.flops)      # of the last forward + backward
 
     # ---- constants / buffers -------------------------------------------------------------------------------------
     def _vec(self, name, n, val):
@@ -261,10 +223,10 @@ class TrainStep(object):
         the whole buffer to the convolution -- no concatenation copy per step (it was 12 x 27 us).  A step's forward and
         backward finish inside one call (loss_dict snapshots the gradients), so a layer's buffer is free again at the next
         step."""
-        Cp = _r32(C + 2)
+        Cp = TP.r32(C + 2)
         # (a prefetched backbone writes the NEXT batch's tensor while this batch's head still reads its own: two alternating buffers
-        # on that path, a third for the plain loop -- self._coord_slot, set by prefetch_backbone)
-        key = (tag, N, H, W, C, self._coord_slot)
+        # on that path, a third for the plain loop -- the pass's coord_slot)
+        key = (tag, N, H, W, C, self.cur.coord_slot)
         t = self._coord_bufs.get(key)
         if t is None:
             t = torch.zeros((N, H, W, Cp), dtype=torch.float32, device=self.dev)
@@ -278,15 +240,16 @@ class TrainStep(object):
     def new_amax(self, N):
         """A zeroed block of per-image maximum slots (one arena, zeroed once per step)."""
         n = N * K.AMAX_FLOATS_PER_IMAGE
-        if self._amax_arena is None or self._amax_next + n > self._amax_arena.numel():
-            self._amax_arena = torch.zeros(max(384 * n, 1 << 16), dtype=torch.float32, device=self.dev)
-            self._amax_next = 0
-        a = self._amax_arena[self._amax_next:self._amax_next + n]
-        self._amax_next += n
+        cur = self.cur
+        if cur.amax_arena is None or cur.amax_next + n > cur.amax_arena.numel():
+            cur.amax_arena = torch.zeros(max(384 * n, 1 << 16), dtype=torch.float32, device=self.dev)
+            cur.amax_next = 0
+        a = cur.amax_arena[cur.amax_next:cur.amax_next + n]
+        cur.amax_next += n
         return a
 
     # ---- parameters in kernel layout ---------------------------------------------------------------------------------
-    def weight(self, key, coord=False):
+    def weight(self, key):
         """-> dict(krsc, planes, Cin): the convolution weight `key` ([K, C, R, S] in the state_dict) as KRSC, padded to a
         multiple of 32 input channels behind a CoordConv; trainable weights keep a MASTER copy here (updated by SGD, written
         back by sync_to_model) and get their bf16 planes re-split every step."""
@@ -295,9 +258,8 @@ class TrainStep(object):
             self._await_params()
         if ent is None:
             w = self.sd[key].detach().float()
-            Kout, Cin, R, S = w.shape
-            Cp = _r32(Cin) if (coord or Cin % 32) else Cin
-            krsc = torch.zeros((Kout, R, S, Cp), dtype=torch.float32, device=self.dev)
+            Cin = w.shape[1]
+            krsc = torch.zeros(TP.kernel_shape(w.shape), dtype=torch.float32, device=self.dev)
             krsc[..., :Cin] = w.permute(0, 2, 3, 1)
             ent = dict(krsc=krsc, planes=None, f16=None, Cin=Cin, trainable=key in self.train_keys)
             self._wcache[key] = ent
@@ -324,22 +286,11 @@ class TrainStep(object):
         convolution weights first (the weight-decay group), then biases and BatchNorm scales / offsets -- so that SGD is two
         launches, the EMA one, and data-parallel ranks average every gradient with ONE all-reduce.  The kernels read the
         parameters through views into `pflat` from now on; sync_to_model() writes them back into the module."""
-        # (the reference decays conv_offset's bias like a weight: custom_layers.py:189-194)
-        convs = [k for k in self.train_keys if k in self._wcache] + [k for k in self.train_keys if k.endswith('.conv_offset.bias')]
-        rest = [k for k in self.train_keys if k not in convs]
-        offs, total = {}, 0
-        for k in convs + rest:
-            shp = tuple(self._wcache[k]['krsc'].shape) if k in self._wcache else tuple(self.sd[k].shape)
-            n = 1
-            for d in shp:
-                n *= d
-            offs[k] = (total, n, shp)
-            total += (n + 63) // 64 * 64
-            if k == convs[-1]:
-                self.n_decay = total                       # [0, n_decay): weight decay applies
+        self.layout, total, self.n_decay = TP.flat_layout(      # {key: (offset, numel, shape)}; [0, n_decay): weight decay applies
+            [(k, tuple(self._wcache[k]['krsc'].shape if k in self._wcache else self.sd[k].shape)) for k in self.train_keys])
         z = lambda: torch.zeros(total, dtype=torch.float32, device=self.dev)
         self.gflat, self.vflat, self.pflat = z(), z(), z()
-        for k, (o, n, shp) in offs.items():
+        for k, (o, n, shp) in self.layout.items():
             self.G[k] = self.gflat[o:o + n].view(shp)
             self.V[k] = self.vflat[o:o + n].view(shp)
             self.P[k] = self.pflat[o:o + n].view(shp)
@@ -378,7 +329,7 @@ class TrainStep(object):
     def coord_concat(self, x):
         """CoordConv.__call__ (reference model/custom_layers.py:261-272) as a real concatenation, zero-padded to a multiple
         of 32 channels for the implicit GEMM: [x, x_range, y_range, 0 ...]."""
-        Cp = _r32(x.C + 2)
+        Cp = TP.r32(x.C + 2)
         if x.coordp == Cp and x.coff == 0:               # produced into a coordinate-ready buffer (new_coord): nothing to copy
             return Act(x.t, 0, Cp, x.req, None if x.amax is None else torch.clamp_min(x.amax, 1.0))
         key = ('coord', x.H, x.W, Cp - x.C)
@@ -448,11 +399,11 @@ class TrainStep(object):
     def conv_unit(self, prefix, x, stride=1, act=None, res=None, coord=False, out=None, coord_out=False):
         """Conv2dUnit.forward in training mode (reference model/custom_layers.py:243-253): conv -> BatchNorm on batch
         statistics -> activation; records its backward when its parameters train."""
-        sd = self.sd
+        sd, cur = self.sd, self.cur
         if prefix + '.conv.dcn_weight' in sd:
             return self._dcn_unit(prefix, x, stride, act)
         wkey = prefix + '.conv.weight'
-        ent = self.weight(wkey, coord)
+        ent = self.weight(wkey)
         trainable = ent['trainable']
         xin = self.coord_concat(x) if coord else x
         krsc = ent['krsc']
@@ -467,70 +418,77 @@ class TrainStep(object):
 
         def get_raw():          # (allocated on first use: a layer whose BatchNorm is applied from the convolution's epilogue never stores it)
             if not raw_box:
-                raw_box.append(self.new(xin.N, Ho, Wo, Kout, ld=_r32(Kout) if not has_bn else None, req=trainable, zero=not has_bn))
+                raw_box.append(self.new(xin.N, Ho, Wo, Kout, ld=TP.r32(Kout) if not has_bn else None, req=trainable, zero=not has_bn))
             return raw_box[0]
         one, b0 = self._vec('one', Kout, 1.0), bias if bias is not None else self._vec('zero', Kout, 0.0)
         use_f16 = self.f16 and xin.amax is not None and ent['f16'] is not None
 
         def run(cfg_id, splitk):
-            K.conv2d_bn_act(xin.view(), krsc, one, b0, get_raw().view(), stride, pad, None, cfg=cfg_id, splitk=splitk, ws=self.ws,
+            K.conv2d_bn_act(xin.view(), krsc, one, b0, get_raw().view(), stride, pad, None, cfg=cfg_id, splitk=splitk, ws=cur.ws,
                             w_x3=None if (use_f16 or self.fp32) else self._planes(ent), w_f16=ent['f16'] if use_f16 else None,
                             amax_in=xin.amax if use_f16 else None)
-        key = 'conv:N%d:H%d:W%d:C%d:K%d:R%d:s%d' % (xin.N, xin.H, xin.W, Cp, Kout, R, stride)
-        cfg_id, splitk = (-1, 0) if self.fp32 else train_fwd_cfg(*self._choose(key, run, R * S * Cp // 32, use_f16))
-        # BatchNorm statistics from the convolution's epilogue (the f16x2 kernels, one split): saves the
-        # statistics kernel's pass over the raw output
-        slices = 0
-        on_stream = cfg_id >= 0 and conv_cfg(cfg_id).family == 'stream'
-        # Frozen 1x1 layers on the streaming kernel (the HBM-bound conv3 / shortcut layers of stage 2): the raw output is never
-        # stored -- one launch for the statistics, one that applies the BatchNorm to its own accumulators (ops.conv1x1_bn_apply)
-        epi = (self.bn_epilogue and has_bn and use_f16 and self.fuse_stats and not trainable and not coord and splitk == 1
-               and on_stream and (R, S, stride) == (1, 1, 1))
-        if (self.bn_epilogue_all and not epi and has_bn and use_f16 and self.fuse_stats and not trainable and not coord and (R, S, stride) == (1, 1, 1)
-                and Cp == 128 and Kout % 128 == 0 and (Kout // 128) & (Kout // 128 - 1) == 0 and Kout // 128 <= 16 and xin.H * xin.W >= 32):
-            epi, cfg_id, splitk = True, K.stream_first_cfg(), 1          # (the C = 128 layers whatever tile the table names: measured +0.8 %)
-        if epi:
+        key = TP.shape_key('conv', xin.N, xin.H, xin.W, Cp, Kout, R, stride)
+        form, cfg_id, splitk = TP.conv_form(has_bn, use_f16, trainable, coord, R, S, stride, Cp, Kout, xin.H * xin.W,
+                                            (-1, 0) if self.fp32 else self._choose(key, run, R * S * Cp // 32, use_f16), self, conv_cfg,
+                                            self._stream0)
+        slices, epi = 0, None
+        if form != 'plain':
             need = K.conv2d_bn_partials_bytes(xin.N * Ho * Wo, Kout) // 4
-            if self._bn_part is None or self._bn_part.numel() < need:
-                self._bn_part = torch.empty(need, dtype=torch.float32, device=self.dev)
-            slices = K.conv1x1_stats(xin.view(), ent['f16'], b0, Kout, conv_cfg(cfg_id).local, xin.amax, self._bn_part)
-        elif has_bn and use_f16 and self.fuse_stats and splitk == 1 and cfg_id >= 0 and conv_cfg(cfg_id).bn_stats:
-            need = K.conv2d_bn_partials_bytes(xin.N * Ho * Wo, Kout) // 4
-            if self._bn_part is None or self._bn_part.numel() < need:
-                self._bn_part = torch.empty(need, dtype=torch.float32, device=self.dev)
-            slices = K.conv2d_train_fwd(xin.view(), krsc, ent['f16'], b0, get_raw().view(), stride, pad, cfg_id, xin.amax, self._bn_part)
+            if cur.bn_part is None or cur.bn_part.numel() < need:
+                cur.bn_part = torch.empty(need, dtype=torch.float32, device=self.dev)
+        if form == 'epilogue':         # ops.conv1x1_stats now, ops.conv1x1_bn_apply in _bn_fwd: the raw output is never stored
+            epi = (xin, ent['f16'], b0, conv_cfg(cfg_id).local)
+            slices = K.conv1x1_stats(xin.view(), ent['f16'], b0, Kout, epi[3], xin.amax, cur.bn_part)
+        elif form == 'stats':
+            slices = K.conv2d_train_fwd(xin.view(), krsc, ent['f16'], b0, get_raw().view(), stride, pad, cfg_id, xin.amax, cur.bn_part)
         else:
             run(cfg_id, splitk)
-        self.flops += 2 * xin.N * Ho * Wo * Kout * R * S * ent['Cin']
+        cur.flops += 2 * xin.N * Ho * Wo * Kout * R * S * ent['Cin']
         raw = None if epi else get_raw()
-        if not has_bn:
-            y = raw
-            mean = invstd = None
-        else:
-            mean = torch.empty(Kout, dtype=torch.float32, device=self.dev)
-            invstd = torch.empty(Kout, dtype=torch.float32, device=self.dev)
-            if slices:
-                K.bn_train_stats_merge(self._bn_part, slices, 1e-5, 0.1, mean, invstd, sd[prefix + '.bn.running_mean'], sd[prefix + '.bn.running_var'])
-            else:
-                K.bn_train_stats(raw.view(), 1e-5, 0.1, mean, invstd, sd[prefix + '.bn.running_mean'], sd[prefix + '.bn.running_var'], self.ws)
-            self._nbt.append(prefix + '.bn.num_batches_tracked')
-            y = out if out is not None else (self.new_coord(prefix, xin.N, Ho, Wo, Kout) if coord_out else self.new(xin.N, Ho, Wo, Kout))
-            y.req = trainable
-            y.amax = self.new_amax(xin.N) if self.f16 else None
-            if epi:
-                K.conv1x1_bn_apply(xin.view(), ent['f16'], b0, mean, invstd, self.param(prefix + '.bn.weight'), self.param(prefix + '.bn.bias'),
-                                   y.view(), act, None if res is None else res.view(), conv_cfg(cfg_id).local, xin.amax, y.amax)
-            else:
-                K.bn_train_apply(raw.view(), mean, invstd, self.param(prefix + '.bn.weight'), self.param(prefix + '.bn.bias'), y.view(), act,
-                                 None if res is None else res.view(), y.amax)
+        y, mean, invstd = (self._bn_fwd(prefix, raw, slices, (xin.N, Ho, Wo, Kout), trainable, act, res, out, coord_out, epi) if has_bn
+                           else (raw, None, None))
         if trainable:
             def bwd_unit():
                 self._conv_unit_bwd(prefix, x, xin, raw, y, mean, invstd, act, stride, pad, ent, res)
                 self._grads_done(prefix)
-            self.tape.append(bwd_unit)
+            cur.tape.append(bwd_unit)
         if self.acts is not None:          # debugging / tests: activations (and, after the backward, their gradients) by layer
             self.acts[prefix] = y
         return y
+
+    def _bn_fwd(self, prefix, raw, slices, shape, trainable, act, res=None, out=None, coord_out=False, epi=None):
+        """BatchNorm on batch statistics + shortcut + activation behind a convolution -> (y, mean, invstd).  The statistics come from
+        `raw`, the convolution's output, or -- slices > 0 -- from that many slices of partials its epilogue left in cur.bn_part.
+        epi = (xin, planes, bias, variant): no raw output exists, the streaming kernel applies to its own accumulators."""
+        sd, cur = self.sd, self.cur
+        N, Ho, Wo, Kout = shape
+        mean = torch.empty(Kout, dtype=torch.float32, device=self.dev)
+        invstd = torch.empty(Kout, dtype=torch.float32, device=self.dev)
+        if slices:
+            K.bn_train_stats_merge(cur.bn_part, slices, 1e-5, 0.1, mean, invstd, sd[prefix + '.bn.running_mean'], sd[prefix + '.bn.running_var'])
+        else:
+            K.bn_train_stats(raw.view(), 1e-5, 0.1, mean, invstd, sd[prefix + '.bn.running_mean'], sd[prefix + '.bn.running_var'], cur.ws)
+        cur.nbt.append(prefix + '.bn.num_batches_tracked')
+        y = out if out is not None else (self.new_coord(prefix, N, Ho, Wo, Kout) if coord_out else self.new(N, Ho, Wo, Kout))
+        y.req = trainable
+        y.amax = self.new_amax(N) if self.f16 else None
+        gamma, beta, r = self.param(prefix + '.bn.weight'), self.param(prefix + '.bn.bias'), None if res is None else res.view()
+        if epi is not None:
+            K.conv1x1_bn_apply(epi[0].view(), epi[1], epi[2], mean, invstd, gamma, beta, y.view(), act, r, epi[3], epi[0].amax, y.amax)
+        else:
+            K.bn_train_apply(raw.view(), mean, invstd, gamma, beta, y.view(), act, r, y.amax)
+        return y, mean, invstd
+
+    def _bn_bwd(self, prefix, raw, y, dy, mean, invstd, act, track):
+        """Backward of _bn_fwd's activation and BatchNorm -> the gradient of `raw`; the scale's and offset's gradients go to self.G.
+        track: give d_raw a tracked-maximum block -- the operand scale of an f16x2 weight / data gradient of a plain convolution.  The
+        DCN unit and the stem pass False: what reads their d_raw (dcnv2_backward and the conv_offset convolution's gradients, the
+        stem's 3-channel weight gradient) runs on the exact kernels, which take no maximum."""
+        d_raw = self.new(raw.N, raw.H, raw.W, raw.C)
+        d_raw.amax = self.new_amax(raw.N) if track else None
+        K.bn_train_bwd(raw.view(), y.view(), dy.view(), mean, invstd, self.param(prefix + '.bn.weight'), d_raw.view(),
+                       self.G[prefix + '.bn.weight'], self.G[prefix + '.bn.bias'], act, self.cur.ws, d_raw.amax)
+        return d_raw
 
     def _prepare_weights(self):
         """Once per step, in front of the first convolution: the f16x2 operand planes of every trainable convolution weight (forward
@@ -571,25 +529,25 @@ class TrainStep(object):
             pe = ent.get('prep')
             if pe is not None and pe.get('dgrad'):
                 C = krsc.shape[3]
-                K.conv2d_dgrad_prepared(d_raw.view(), pe, dxin.view(), pad, self._vec('one', C, 1.0), self._vec('zero', C, 0.0), self.ws,
+                K.conv2d_dgrad_prepared(d_raw.view(), pe, dxin.view(), pad, self._vec('one', C, 1.0), self._vec('zero', C, 0.0), self.cur.ws,
                                         cfg=cfg_id, splitk=splitk, amax_dy=amax)
                 return
         if stride == 1:
-            K.conv2d_dgrad(d_raw.view(), krsc, dxin.view(), 1, pad, self.ws, cfg=cfg_id, splitk=splitk, amax_dy=amax)
+            K.conv2d_dgrad(d_raw.view(), krsc, dxin.view(), 1, pad, self.cur.ws, cfg=cfg_id, splitk=splitk, amax_dy=amax)
             return
         R = krsc.shape[1]
         H1, W1 = dxin.H + 2 * pad - R + 1, dxin.W + 2 * pad - R + 1
-        up = self.new(d_raw.N, H1, W1, d_raw.C, ld=_r32(d_raw.C), zero=d_raw.C % 32 != 0)
+        up = self.new(d_raw.N, H1, W1, d_raw.C, ld=TP.r32(d_raw.C), zero=d_raw.C % 32 != 0)
         K.zero_insert(d_raw.view(), up.view(), stride)
-        K.conv2d_dgrad(up.view(), krsc, dxin.view(), 1, pad, self.ws, amax_dy=amax)       # (zeros do not raise the maximum)
+        K.conv2d_dgrad(up.view(), krsc, dxin.view(), 1, pad, self.cur.ws, amax_dy=amax)       # (zeros do not raise the maximum)
 
     def _wgrad(self, xin, d_raw, dw, stride, pad, amax_x, amax_dy):
         """Weight gradient of a convolution; with the side stream, issued there behind everything queued so far."""
         if not self._wgrad_side:
-            K.conv2d_wgrad(xin.view(), d_raw.view(), dw, stride, pad, self.ws, amax_x, amax_dy)
+            K.conv2d_wgrad(xin.view(), d_raw.view(), dw, stride, pad, self.cur.ws, amax_x, amax_dy)
             return
         if self._ws_side is None:
-            self._ws_side = torch.empty_like(self.ws)
+            self._ws_side = torch.empty_like(self.cur.ws)
         main = torch.cuda.current_stream(self.dev)
         self._wstream.wait_stream(main)
         with torch.cuda.stream(self._wstream):
@@ -608,7 +566,6 @@ class TrainStep(object):
         dy = y.g
         if dy is None:
             raise PPYoloHipError('%s: no gradient reached this layer' % prefix)
-        sd = self.sd
         if res is not None:
             # y = act(bn(conv) + res): the gradient in front of the activation goes to both branches
             dz = self.new(y.N, y.H, y.W, y.C)
@@ -618,21 +575,18 @@ class TrainStep(object):
             dy, act = dz, None
         f16 = self.f16 and xin.amax is not None       # weight gradient on the f16x2 kernel: both operands' maxima are tracked
         if mean is not None:
-            d_raw = self.new(raw.N, raw.H, raw.W, raw.C)
-            d_raw.amax = self.new_amax(raw.N) if f16 else None
-            K.bn_train_bwd(raw.view(), y.view(), dy.view(), mean, invstd, self.param(prefix + '.bn.weight'), d_raw.view(),
-                           self.G[prefix + '.bn.weight'], self.G[prefix + '.bn.bias'], act, self.ws, d_raw.amax)
+            d_raw = self._bn_bwd(prefix, raw, y, dy, mean, invstd, act, track=f16)
         else:
             d_raw = dy
             if f16 and d_raw.amax is None:
                 d_raw.amax = K.amax_slots(d_raw.t)      # (the loss gradient of an output convolution: three small tensors per step)
-            K.channel_sum(dy.view(), self.G[prefix + '.conv.bias'], self.ws)
+            K.channel_sum(dy.view(), self.G[prefix + '.conv.bias'], self.cur.ws)
         self._wgrad(xin, d_raw, self.G[prefix + '.conv.weight'], stride, pad,
                     xin.amax if f16 and d_raw.amax is not None else None, d_raw.amax if f16 else None)
         unit = 2 * raw.N * raw.H * raw.W * raw.C * ent['krsc'].shape[1] * ent['krsc'].shape[2] * ent['Cin']
-        self.flops += unit
+        self.cur.flops += unit
         if x.req:
-            self.flops += unit
+            self.cur.flops += unit
             dxin = self.new(xin.N, xin.H, xin.W, xin.C)
             Kk, R = ent['krsc'].shape[0], ent['krsc'].shape[1]
 
@@ -640,9 +594,8 @@ class TrainStep(object):
             if stride == 1:
                 def run(cfg_id, splitk):
                     self._dgrad(d_raw, ent['krsc'], dxin, 1, pad, cfg_id, splitk, df16, ent)
-                # the data gradient runs the forward kernel on the transposed geometry: C' = K rounded up to 32, K' = C
-                run(*self._choose('conv:N%d:H%d:W%d:C%d:K%d:R%d:s1' % (raw.N, raw.H, raw.W, _r32(Kk), xin.C, R), run, R * R * _r32(Kk) // 32,
-                                  df16))
+                key, chunks = TP.dgrad_key(raw.N, raw.H, raw.W, Kk, xin.C, R)      # (the forward kernel on the transposed geometry)
+                run(*self._choose(key, run, chunks, df16))
             else:
                 self._dgrad(d_raw, ent['krsc'], dxin, stride, pad, f16=df16)
             self.accum(x, dxin.slice(0, x.C))
@@ -650,47 +603,36 @@ class TrainStep(object):
     def _dcn_unit(self, prefix, x, stride, act):
         """DCNv2 inside a backbone unit: offsets / masks from conv_offset, deformable contraction, BatchNorm on batch statistics
         (reference model/custom_layers.py:551-677); records its backward when stage 5 trains (freeze_at < 5)."""
-        sd = self.sd
         co = self.weight(prefix + '.conv.conv_offset.weight')
         trainable = co['trainable']
         Ho, Wo = K.dcn_out_hw(x.H, x.W, stride, 1)
         om = self.new(x.N, Ho, Wo, 27, ld=32, zero=True)
         K.conv2d_bn_act(x.view(), co['krsc'], self._vec('one', 27, 1.0), self.param(prefix + '.conv.conv_offset.bias'), om.view(), stride, 1,
-                        None, ws=self.ws, w_x3=None if self.fp32 else self._planes(co))
+                        None, ws=self.cur.ws, w_x3=None if self.fp32 else self._planes(co))
         w = self.weight(prefix + '.conv.dcn_weight')
         Kout = w['krsc'].shape[0]
         raw = self.new(x.N, Ho, Wo, Kout)
         use_f16 = self.f16 and x.amax is not None and w['f16'] is not None
-        ent = (self._tuned_f if use_f16 else self._tuned).get('dcnf:N%d:H%d:W%d:C%d:K%d:R3:s%d%s' % (x.N, x.H, x.W, x.C, Kout, stride,
-                                                                                                ':f' if use_f16 else ''))
+        ent = (self._tuned_f if use_f16 else self._tuned).get(TP.shape_key('dcnf', x.N, x.H, x.W, x.C, Kout, 3, stride, f=use_f16))
         K.dcnv2(x.view(), w['krsc'], self._vec('one', Kout, 1.0), self._vec('zero', Kout, 0.0), om.view(), raw.view(), stride, 1, None,
-                self.ws, cfg=ent[0] if (ent and not self.fp32) else -1, splitk=ent[1] if (ent and not self.fp32) else 0,
+                self.cur.ws, cfg=ent[0] if (ent and not self.fp32) else -1, splitk=ent[1] if (ent and not self.fp32) else 0,
                 w_x3=None if (use_f16 or self.fp32) else self._planes(w), w_f16=w['f16'] if use_f16 else None,
                 amax_in=x.amax if use_f16 else None)
-        self.flops += 2 * x.N * Ho * Wo * (Kout * 9 * x.C + 27 * 9 * x.C)
-        mean = torch.empty(Kout, dtype=torch.float32, device=self.dev)
-        invstd = torch.empty(Kout, dtype=torch.float32, device=self.dev)
-        K.bn_train_stats(raw.view(), 1e-5, 0.1, mean, invstd, sd[prefix + '.bn.running_mean'], sd[prefix + '.bn.running_var'], self.ws)
-        self._nbt.append(prefix + '.bn.num_batches_tracked')
-        y = self.new(x.N, Ho, Wo, Kout, req=trainable)
-        y.amax = self.new_amax(x.N) if self.f16 else None
-        K.bn_train_apply(raw.view(), mean, invstd, self.param(prefix + '.bn.weight'), self.param(prefix + '.bn.bias'), y.view(), act, None,
-                         y.amax)
+        self.cur.flops += 2 * x.N * Ho * Wo * (Kout * 9 * x.C + 27 * 9 * x.C)
+        y, mean, invstd = self._bn_fwd(prefix, raw, 0, (x.N, Ho, Wo, Kout), trainable, act)
 
         def bwd():
             if y.g is None:
                 raise PPYoloHipError('%s: no gradient reached this layer' % prefix)
-            d_raw = self.new(raw.N, raw.H, raw.W, raw.C)
-            K.bn_train_bwd(raw.view(), y.view(), y.g.view(), mean, invstd, self.param(prefix + '.bn.weight'), d_raw.view(),
-                           self.G[prefix + '.bn.weight'], self.G[prefix + '.bn.bias'], act, self.ws)
+            d_raw = self._bn_bwd(prefix, raw, y, y.g, mean, invstd, act, track=False)
             dxs = self.new(x.N, x.H, x.W, x.C)
             d_om = self.new(x.N, Ho, Wo, 27, ld=32, zero=True)
             K.dcnv2_backward(x.view(), w['krsc'], om.view(), d_raw.view(), dxs.view(), d_om.view(), self.G[prefix + '.conv.dcn_weight'],
-                             stride, 1, self.ws)
+                             stride, 1, self.cur.ws)
             # conv_offset: a plain 3x3 convolution with bias, same stride, whose output gradient is d_om
-            K.conv2d_wgrad(x.view(), d_om.view(), self.G[prefix + '.conv.conv_offset.weight'], stride, 1, self.ws)
-            K.channel_sum(d_om.view(), self.G[prefix + '.conv.conv_offset.bias'], self.ws)
-            self.flops += 2 * 2 * x.N * Ho * Wo * (Kout * 9 * x.C + 27 * 9 * x.C)
+            K.conv2d_wgrad(x.view(), d_om.view(), self.G[prefix + '.conv.conv_offset.weight'], stride, 1, self.cur.ws)
+            K.channel_sum(d_om.view(), self.G[prefix + '.conv.conv_offset.bias'], self.cur.ws)
+            self.cur.flops += 2 * 2 * x.N * Ho * Wo * (Kout * 9 * x.C + 27 * 9 * x.C)
             if x.req:
                 self.accum(x, dxs)
                 dxo = self.new(x.N, x.H, x.W, x.C)
@@ -698,7 +640,7 @@ class TrainStep(object):
                 self.accum(x, dxo)
             self._grads_done(prefix)
         if trainable:
-            self.tape.append(bwd)
+            self.cur.tape.append(bwd)
         return y
 
     def accum(self, x, g):
@@ -709,7 +651,7 @@ class TrainStep(object):
 
     # ---- backbone (stages 1 .. freeze_at forward only; the stages above record their backward like the head) -----------------
     def _stem(self, x_nchw):
-        sd, p = self.sd, 'backbone.stage1_conv1_1'
+        p = 'backbone.stage1_conv1_1'
         ent = self.weight(p + '.conv.weight')                  # (KRSC master, 3 channels padded to 32; the stem kernel reads KCRS)
         trainable = ent['trainable']
         N, _, H, W = x_nchw.shape
@@ -718,27 +660,19 @@ class TrainStep(object):
         raw = self.new(N, Ho, Wo, Kout)
         K.stem_conv(x_nchw, ent['krsc'][..., :3].permute(0, 3, 1, 2).contiguous(), self._vec('one', Kout, 1.0), self._vec('zero', Kout, 0.0),
                     raw.view(), None)
-        mean = torch.empty(Kout, dtype=torch.float32, device=self.dev)
-        invstd = torch.empty(Kout, dtype=torch.float32, device=self.dev)
-        K.bn_train_stats(raw.view(), 1e-5, 0.1, mean, invstd, sd[p + '.bn.running_mean'], sd[p + '.bn.running_var'], self.ws)
-        self._nbt.append(p + '.bn.num_batches_tracked')
-        y0 = self.new(N, Ho, Wo, Kout, req=trainable)
-        y0.amax = self.new_amax(N) if self.f16 else None
-        K.bn_train_apply(raw.view(), mean, invstd, self.param(p + '.bn.weight'), self.param(p + '.bn.bias'), y0.view(), 'relu', None, y0.amax)
+        y0, mean, invstd = self._bn_fwd(p, raw, 0, (N, Ho, Wo, Kout), trainable, 'relu')
         if trainable:                                          # freeze_at = 0: the first convolution's weight gradient (no data gradient: the image)
             def bwd():
-                d_raw = self.new(N, Ho, Wo, Kout)
-                K.bn_train_bwd(raw.view(), y0.view(), y0.g.view(), mean, invstd, self.param(p + '.bn.weight'), d_raw.view(),
-                               self.G[p + '.bn.weight'], self.G[p + '.bn.bias'], 'relu', self.ws)
+                d_raw = self._bn_bwd(p, raw, y0, y0.g, mean, invstd, 'relu', track=False)
                 x4 = torch.zeros((N, H, W, 4), dtype=torch.float32, device=self.dev)
                 x4[..., :3] = x_nchw.permute(0, 2, 3, 1)
                 dw3 = torch.empty((Kout, 3, 3, 3), dtype=torch.float32, device=self.dev)
-                K.conv2d_wgrad(K.View(x4, 0, 3), d_raw.view(), dw3, 2, 1, self.ws)
+                K.conv2d_wgrad(K.View(x4, 0, 3), d_raw.view(), dw3, 2, 1, self.cur.ws)
                 g = self.G[p + '.conv.weight']
                 g.zero_()
                 g[..., :3] = dw3
                 self._grads_done(p)
-            self.tape.append(bwd)
+            self.cur.tape.append(bwd)
         y = self.conv_unit('backbone.stage1_conv1_2', y0, 1, 'relu')
         y = self.conv_unit('backbone.stage1_conv1_3', y, 1, 'relu')
         Hp, Wp = K.conv_out_hw(y.H, y.W, 3, 3, 2, 1)
@@ -750,7 +684,7 @@ class TrainStep(object):
                 g = self.new(y.N, y.H, y.W, y.C)
                 K.maxpool3x3s2_bwd(y.view(), o.g.view(), g.view())
                 self.accum(y, g)
-            self.tape.append(pool_bwd)
+            self.cur.tape.append(pool_bwd)
         return o
 
     def _avgpool(self, x):
@@ -762,7 +696,7 @@ class TrainStep(object):
                 g = self.new(x.N, x.H, x.W, x.C)
                 K.avgpool2x2_bwd(o.g.view(), g.view())
                 self.accum(x, g)
-            self.tape.append(bwd)
+            self.cur.tape.append(bwd)
         return o
 
     def _bottleneck(self, p, x, stride, has_proj, is_first, coord_out=False):
@@ -819,7 +753,7 @@ class TrainStep(object):
                 # (the host runs ahead of the device); allocated there too, so that no block the main stream has just freed --
                 # and may still be reading -- is written early
                 if self._ws_side is None:
-                    self._ws_side = torch.empty_like(self.ws)
+                    self._ws_side = torch.empty_like(self.cur.ws)
                 main = torch.cuda.current_stream(self.dev)
                 with torch.cuda.stream(self._wstream):
                     m = torch.empty((x.N, x.H, x.W, x.C), dtype=torch.float32, device=self.dev)
@@ -831,7 +765,7 @@ class TrainStep(object):
             else:
                 m = torch.empty((x.N, x.H, x.W, x.C), dtype=torch.float32, device=self.dev)
                 scale = torch.empty(1, dtype=torch.float32, device=self.dev)
-                K.dropblock_mask(m, scale, keep_prob, seed, ws=self.ws)
+                K.dropblock_mask(m, scale, keep_prob, seed, ws=self.cur.ws)
         y = self.new(x.N, x.H, x.W, x.C, req=True) if coord_tag is None else self.new_coord(coord_tag, x.N, x.H, x.W, x.C, req=True)
         y.amax = None if x.amax is None else x.amax * scale     # y = x * mask * scale, mask in {0, 1}
         K.dropblock_apply(x.view(), m, scale, y.view())
@@ -840,48 +774,37 @@ class TrainStep(object):
             g = self.new(x.N, x.H, x.W, x.C)
             K.dropblock_apply(y.g.view(), m, scale, g.view())
             self.accum(x, g)
-        self.tape.append(bwd)
+        self.cur.tape.append(bwd)
         return y
 
     def detection_block(self, p, x, hcfg, is_first):
         """DetectionBlock.__call__ (reference model/head.py:146-231); layer indices as in the state_dict keys."""
-        nblk, coord = hcfg.get('conv_block_num', 2), hcfg.get('coord_conv', True)
-        use_spp, drop, keep = hcfg.get('spp', True), hcfg.get('drop_block', True), hcfg.get('keep_prob', 0.9)
-        active = hcfg.get('drop_active', True)
-        idx = 0
-        # (coord_out / coord_tag: the tensor's one consumer is a CoordConv -> produced into that layer's coordinate-ready buffer)
-        for j in range(nblk):
-            last = j == nblk - 1
-            drop_here = drop and active and ((j == 0 and not is_first) or (last and is_first))
-            if use_spp and is_first and j == 1:
-                Cw = self.sd['%s.layers.%d.conv.weight' % (p, idx + 1)].shape[0]
-                wide = self.new(x.N, x.H, x.W, 4 * Cw, req=True)
-                slot0 = wide.slice(0, Cw)
-                self.conv_unit('%s.layers.%d' % (p, idx + 1), x, 1, 'leaky', coord=coord, out=slot0)
+        route = None
+        for st in TP.detection_schedule(hcfg, is_first):
+            name = '%s.layers.%d' % (p, st.n)
+            if st.kind == 'spp':
                 K.spp(slot0.view(), wide.slice(Cw, Cw).view(), wide.slice(2 * Cw, Cw).view(), wide.slice(3 * Cw, Cw).view())
                 wide.amax = slot0.amax                             # (max-pooled copies of slot 0)
 
                 def spp_bwd(wide=wide, slot0=slot0, Cw=Cw):
                     g = self.new(wide.N, wide.H, wide.W, Cw)
-                    K.spp_bwd(slot0.view(), wide.g.view(), g.view(), self.ws)
+                    K.spp_bwd(slot0.view(), wide.g.view(), g.view(), self.cur.ws)
                     self.accum(slot0, g)
-                self.tape.append(spp_bwd)
-                x = self.conv_unit('%s.layers.%d' % (p, idx + 3), wide, 1, 'leaky')
-                x = self.conv_unit('%s.layers.%d' % (p, idx + 4), x, 1, 'leaky', coord_out=coord and not drop_here)
-                idx += 5
-            else:
-                x = self.conv_unit('%s.layers.%d' % (p, idx + 1), x, 1, 'leaky', coord=coord)
-                x = self.conv_unit('%s.layers.%d' % (p, idx + 2), x, 1, 'leaky', coord_out=coord and not drop_here)
-                idx += 3
-            if drop and j == 0 and not is_first:
-                x = self.drop_block(x, keep, '%s.drop%d' % (p, j) if coord else None) if active else x
-                idx += 1
-        if drop and is_first:
-            x = self.drop_block(x, keep, '%s.drop_last' % p if coord else None) if active else x
-            idx += 1
-        route = self.conv_unit('%s.layers.%d' % (p, idx + 1), x, 1, 'leaky', coord=coord, coord_out=coord)
-        tip = self.conv_unit('%s.tip_layers.1' % p, route, 1, 'leaky', coord=coord)
-        return route, tip
+                self.cur.tape.append(spp_bwd)
+                x = wide
+            elif st.kind == 'drop':
+                if hcfg.get('drop_active', True):
+                    x = self.drop_block(x, hcfg.get('keep_prob', 0.9), name if st.dest == 'coord' else None)
+            elif st.kind == 'tip':
+                return route, self.conv_unit('%s.tip_layers.%d' % (p, st.n), route, 1, 'leaky', coord=st.coord)
+            elif st.dest == 'spp':         # into slot 0 of the buffer the SPP step fills up
+                Cw = self.sd[name + '.conv.weight'].shape[0]
+                wide = self.new(x.N, x.H, x.W, 4 * Cw, req=True)
+                slot0 = wide.slice(0, Cw)
+                self.conv_unit(name, x, 1, 'leaky', coord=st.coord, out=slot0)
+            else:                          # 'conv' / 'route'
+                x = self.conv_unit(name, x, 1, 'leaky', coord=st.coord, coord_out=st.dest == 'coord')
+                route = x if st.kind == 'route' else route
 
     def head(self, feats):
         """YOLOv3Head._get_outputs (reference model/head.py:381-398)."""
@@ -907,7 +830,7 @@ class TrainStep(object):
                         gf = self.new(feat.N, feat.H, feat.W, feat.C)
                         gf.t.copy_(wide.g.t[..., wide.g.coff + Cr:wide.g.coff + Cr + feat.C])
                         self.accum(feat, gf)
-                self.tape.append(up_bwd)
+                self.cur.tape.append(up_bwd)
                 blk = wide
             else:
                 blk = feat
@@ -925,12 +848,10 @@ class TrainStep(object):
         1e-3 can disagree on a sign there; the loss kernel is checked on identical inputs in tests/test_gpu_train_ops.py)."""
         if not x_nchw.is_cuda:
             raise PPYoloHipError('the training step needs ROCm device tensors; there is no CPU path')
-        self.tape = []
-        self.flops = 0
+        cur = self.cur
+        cur.tape, cur.flops = [], 0
         self._prep_done = False          # a step that raised after _prepare_weights() must not leave stale f16x2 planes behind
-        if self._amax_arena is not None:
-            self._amax_arena.zero_()
-            self._amax_next = 0
+        cur.zero_amax()
         self.masks = list(dropblock_masks) if dropblock_masks is not None else None
         pref, self._pref = self._pref, None
         with torch.no_grad():
@@ -945,8 +866,8 @@ class TrainStep(object):
                 feats = pref['feats']
                 for f in feats:
                     f.t.record_stream(main)          # (allocated under the side stream: not to be reused before the head has read it)
-                self._nbt = list(pref['nbt']) + self._nbt
-                self.flops += pref['flops']
+                cur.nbt = list(pref['nbt']) + cur.nbt
+                cur.flops += pref['flops']
             else:
                 if pref is not None:
                     # a prefetch that is not used (another tensor, or the same one modified since): its backbone has already
@@ -980,34 +901,30 @@ class TrainStep(object):
             return False
         if self._bstream is None:
             self._bstream = torch.cuda.Stream(device=self.dev)
-            self._b_res = [torch.empty_like(self.ws), None, [None, None], 0]
+            self._b_res = [torch.empty_like(self.cur.ws), None, [None, None], 0]
         main = torch.cuda.current_stream(self.dev)
         if ready is None:
             ready = torch.cuda.Event()
             ready.record(main)
         res = self._b_res
         res[3] ^= 1
-        saved = (self.ws, self._bn_part, self._amax_arena, self._amax_next, self._nbt, self.flops, self.tape)
-        self._coord_slot = res[3]
+        # the backbone runs under a pass of its own: the side stream's workspace and partials, this alternation's arena and coordinate slot
+        prev, self.cur = self.cur, Pass(res[0], res[3], res[1], res[2][res[3]])
         self._bstream.wait_event(ready)
         try:
             with torch.cuda.stream(self._bstream), torch.no_grad():
-                self.ws, self._bn_part = res[0], res[1]
-                self._amax_arena, self._amax_next = res[2][res[3]], 0
-                if self._amax_arena is not None:
-                    self._amax_arena.zero_()
-                self._nbt, self.flops, self.tape = [], 0, []
+                cur = self.cur
+                cur.zero_amax()
                 feats = self.backbone(x_next.float().contiguous())
-                assert not self.tape, 'prefetch_backbone: a frozen backbone records no backward'
+                assert not cur.tape, 'prefetch_backbone: a frozen backbone records no backward'
                 ev = torch.cuda.Event()
                 ev.record(self._bstream)
                 x_next.record_stream(self._bstream)          # (the allocator must not hand its block out while the side stream reads it)
                 # the tensor itself is kept: identity + version decide whether the features are served (an address can be reused)
-                self._pref = dict(x=x_next, key=self._pref_key(x_next), feats=feats, event=ev, nbt=self._nbt, flops=self.flops)
-                res[1], res[2][res[3]] = self._bn_part, self._amax_arena
+                self._pref = dict(x=x_next, key=self._pref_key(x_next), feats=feats, event=ev, nbt=cur.nbt, flops=cur.flops)
+                res[1], res[2][res[3]] = cur.bn_part, cur.amax_arena      # (grown on demand during the pass)
         finally:
-            self.ws, self._bn_part, self._amax_arena, self._amax_next, self._nbt, self.flops, self.tape = saved
-            self._coord_slot = 2
+            self.cur = prev
         return True
 
     def head_loss_backward(self, feats, gt_box, targets, inject_douts=None):
@@ -1016,7 +933,7 @@ class TrainStep(object):
         try:
             return self._head_loss_backward(feats, gt_box, targets, inject_douts, cfg, hcfg)
         finally:
-            self.tape = []
+            self.cur.tape = []
             self._prep_done = False
             self._join_wgrad()           # (also after an exception: nothing of this step stays queued behind freed operands)
             # BatchNorm running statistics / counters were written through raw pointers (no autograd version bump) and the
@@ -1029,7 +946,7 @@ class TrainStep(object):
         with torch.no_grad():
             self._prepare_weights()
             outs = self.head(feats)
-            if self._nbt:      # BatchNorm's num_batches_tracked of every layer this forward normalised: one launch
+            if self.cur.nbt:      # BatchNorm's num_batches_tracked of every layer this forward normalised: one launch
                 self._bump_counters()
             if self.gflat is None:
                 self._alloc_flat()
@@ -1043,11 +960,11 @@ class TrainStep(object):
                 K.yolov3_loss(out.view(), targets[i].float().contiguous(), gt_box.float().contiguous(), anchors, hcfg['num_classes'],
                               hcfg['downsample'][i], cfg.yolo_loss['scale_x_y'], cfg.yolo_loss['ignore_thresh'], cfg.iou_loss['loss_weight'],
                               iou_aware, cfg.iou_aware_loss['loss_weight'] if iou_aware else 0.0, dout.view(), loss6, accumulate=i > 0,
-                              ws=self.ws, amax_dout=dout.amax, iou_loss_square=cfg.iou_loss.get('loss_square', True))
+                              ws=self.cur.ws, amax_dout=dout.amax, iou_loss_square=cfg.iou_loss.get('loss_square', True))
                 if inject_douts is not None:
                     dout.t[..., :out.C].copy_(inject_douts[i].to(self.dev).permute(0, 2, 3, 1))
                 out.g = dout
-            for fn in reversed(self.tape):
+            for fn in reversed(self.cur.tape):
                 fn()
             self._join_wgrad()
         self.outs = outs
@@ -1060,7 +977,7 @@ class TrainStep(object):
         int64 buffers; torch._foreach_add_ on them turned out to be 72 tiny device copies per step (0.35 ms: rocprofv3,
         tools/probes/train_copy_probe.py).  They become views into ONE flat tensor (the modules' buffers are re-bound to the views,
         values kept; state_dict() keeps returning one 0-dim tensor per layer) and the bump is one `add_`."""
-        keys, self._nbt = self._nbt, []
+        keys, self.cur.nbt = self.cur.nbt, []
         if self._nbt_keys != keys or any(self.sd[k].data_ptr() != self._nbt_flat[i].data_ptr() for i, k in enumerate(keys)):
             try:
                 flat = torch.stack([self.sd[k].detach().to(torch.int64) for k in keys])
@@ -1075,55 +992,16 @@ class TrainStep(object):
         self._nbt_flat.add_(1)
 
     # ---- data parallelism: gradient averaging overlapped with the backward --------------------------------------------------------
-    @staticmethod
-    def _bucket_of(key):
-        """Gradient bucket of a parameter: a detection block, the head's output / transition convolutions, a backbone stage --
-        the units in which the backward finishes its gradients (last layers first)."""
-        q = key.split('.')
-        if q[0] == 'backbone':
-            return q[1][:6]                      # 'stage5'
-        return '.'.join(q[:3]) if q[1] == 'detection_blocks' else 'head.tail'
-
-    def _make_buckets(self):
-        """{bucket: [pending unit count, [(start, end) ranges of gflat]]}: the keys of a bucket are (nearly) contiguous in
-        both parameter groups of the flat layout, so a bucket is two or three ranges."""
-        base = self.gflat.data_ptr()
-        spans, units = {}, {}
-        for k in self.train_keys:
-            b = self._bucket_of(k)
-            o = (self.G[k].data_ptr() - base) // 4
-            spans.setdefault(b, []).append((o, o + (self.G[k].numel() + 63) // 64 * 64))
-            units.setdefault(b, set()).add(self._unit_of(k))
-        self._buckets = {}
-        for b, iv in spans.items():
-            iv.sort()
-            merged = [list(iv[0])]
-            for a, e in iv[1:]:
-                if a <= merged[-1][1]:
-                    merged[-1][1] = max(merged[-1][1], e)
-                else:
-                    merged.append([a, e])
-            self._buckets[b] = dict(units=units[b], ranges=[(a, min(e, self.gflat.numel())) for a, e in merged])
-
-    @staticmethod
-    def _unit_of(key):
-        """The Conv2dUnit prefix a parameter key belongs to ('....conv.weight' / '.bn.bias' / '.conv.conv_offset.bias' ...)."""
-        for tail in ('.conv.conv_offset.weight', '.conv.conv_offset.bias', '.conv.dcn_weight', '.conv.weight', '.conv.bias', '.bn.weight',
-                     '.bn.bias'):
-            if key.endswith(tail):
-                return key[:-len(tail)]
-        return key
-
     def _grads_done(self, prefix):
         """All gradients of unit `prefix` are written: when that completes a bucket, start its all-reduce while the rest of
         the backward runs (the collective is queued behind the kernels issued so far and proceeds on RCCL's own stream)."""
         if self.world <= 1 or not self.overlap or self.gflat is None:
             return
         if self._buckets is None:
-            self._make_buckets()
+            self._buckets = TP.buckets(self.train_keys, self.layout, self.gflat.numel())
         if not self._pending:
             self._pending = {b: set(v['units']) for b, v in self._buckets.items()}
-        b = self._bucket_of(prefix + '.conv.weight')
+        b = TP.bucket_of(prefix + '.conv.weight')
         left = self._pending.get(b)
         if left is None:
             return
@@ -1207,12 +1085,11 @@ class TrainStep(object):
         out = {}
         if self.gflat is None:
             raise PPYoloHipError('grads(): no step has run yet (the flat gradient buffer is allocated by the first one)')
-        base = self.gflat.data_ptr()
         for k in self.train_keys:
             g = self.G[k]
             if flat is not None:
-                o = (g.data_ptr() - base) // 4
-                g = flat[o:o + g.numel()].view(g.shape)
+                o, n, shp = self.layout[k]
+                g = flat[o:o + n].view(shp)
             if k in self._wcache:
                 out[k] = g[..., :self._wcache[k]['Cin']].permute(0, 3, 1, 2).contiguous()
             else:
@@ -1229,11 +1106,9 @@ class TrainStep(object):
         if ema and src is None:
             raise PPYoloHipError('EMA is off (cfg.use_ema)')
         if self.gflat is not None:
-            base = self.pflat.data_ptr()
             for k in self.train_keys:
-                v = self.P[k]
-                o = (v.data_ptr() - base) // 4
-                t = src[o:o + v.numel()].view(v.shape)
+                o, n, shp = self.layout[k]
+                t = src[o:o + n].view(shp)
                 if k in self._wcache:
                     self.sd[k].copy_(t[..., :self._wcache[k]['Cin']].permute(0, 3, 1, 2))
                 else:

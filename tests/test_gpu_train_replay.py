@@ -12,13 +12,14 @@ import launch_replay as lr
 from conftest import build_model
 from config import PPYOLO_2x_Config, PPYOLO_r18vd_Config
 from ppyolo_hip import ops, synth
+from ppyolo_hip.train_plan import shape_key
 from test_gpu_train_step import synth_targets
 
 pytestmark = pytest.mark.gpu
 
 
 def _key_of(rec):
-    return 'conv:N%d:H%d:W%d:C%d:K%d:R%d:s%d' % rec['geom']
+    return shape_key('conv', *rec['geom'])
 
 
 def _prepare(cfgc, S, N, freeze_at):

@@ -133,7 +133,6 @@ def test_r50_head_backward_strict():
     losses = trn.yolov3_loss(outs, targets, gt, cfg)
     sum(losses.values()).backward()
     ts = TrainStep(model, cfg)
-    ts.tape = []
     ts.masks = list(masks)
     fa = [Act(f.permute(0, 2, 3, 1).contiguous().cuda()) for f in feats]
     loss6 = ts.head_loss_backward(fa, gt.cuda(), [t.cuda() for t in targets])
@@ -395,7 +394,6 @@ def test_stage5_blocks_backward_strict():
     dy = torch.randn(y.shape, generator=g) / y.numel() ** 0.5
     y.backward(dy)
     ts = TrainStep(model, cfg)
-    ts.tape, ts._nbt = [], []
     xin = Act(x.permute(0, 2, 3, 1).contiguous().cuda(), 0, 1024, True)
     with torch.no_grad():
         out = xin
@@ -406,7 +404,7 @@ def test_stage5_blocks_backward_strict():
         print('stage 5 output: max error %.2e of the maximum' % e)
         assert e <= 2e-4
         out.g = Act(dy.permute(0, 2, 3, 1).contiguous().cuda(), 0, out.C)
-        for fn in reversed(ts.tape):
+        for fn in reversed(ts.cur.tape):
             fn()
     torch.cuda.synchronize()
     grads = ts.grads()

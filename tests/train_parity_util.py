@@ -174,7 +174,6 @@ def head_only(cfg, sd, model, feats, gt, targets, masks):
             hip_signs[prefix] = (y.dense_nchw() > 0).cpu()
         return y
     ts.conv_unit = hip_cu
-    ts.tape, ts._nbt = [], []
     ts.masks = [m.float() for m in masks] if masks is not None else None
     if masks is None:
         cfg.head['drop_active'] = False

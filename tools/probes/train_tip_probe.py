@@ -54,7 +54,6 @@ for tag, dt in (('ref32', torch.float32), ('ref64', torch.float64)):
     res[tag] = dict(g={k: v.grad for k, v in rec.items()}, w={k: state[k].grad for k in trn.trainable_keys(sd)})
 orc.drop_block_train = real_db
 ts = TrainStep(model, cfg)
-ts.tape, ts._nbt = [], []
 hip_acts = {}
 real_unit = ts.conv_unit
 

@@ -22,7 +22,6 @@ hc = cfg.head
 gt = torch.from_numpy(bb)
 targets = [torch.from_numpy(t) for t in gt2yolo_target(bb, cc, ss, hc['anchors'], hc['anchor_masks'], hc['downsample'], 80, S)]
 ts = TrainStep(model, cfg)
-ts.tape, ts._nbt = [], []
 cap = {}
 real_bwd, real_wg = K.bn_train_bwd, K.conv2d_wgrad
 
