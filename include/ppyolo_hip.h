@@ -763,6 +763,86 @@ int ppy_jpeg_entropy_twin(int n, const void *h_plan, const void *plan, const voi
                           size_t coef_bytes, int *status, void *ws, size_t ws_bytes);
 const char *ppy_jpeg_reason_string(int reason);
 
+/* ------------------------------------------------------------------------------------
+ * Baseline JPEG ENCODING, byte for byte with libjpeg-turbo's defaults -- jpeg_set_defaults, jpeg_set_quality(q, TRUE),
+ * JDCT_ISLOW forward DCT, the standard (Annex K) Huffman tables without optimize_coding, a JFIF 1.01 header with units 0 and
+ * density 1:1 -- i.e. the file cv2.imwrite(path, img, [IMWRITE_JPEG_QUALITY, q]) writes (reference demo.py:50) and Pillow's
+ * Image.save(buf, 'JPEG', quality=q, subsampling=s, restart_marker_blocks=r).  DESIGN.md section 10b.
+ *
+ * Input: uint8 DEVICE images, components = 3 (HWC BGR, pixel stride 3; written as YCbCr with luma sampling h_samp x v_samp =
+ * 1x1, 2x1 or 2x2 and chroma 1x1) or components = 1 ([h][w]; written as a one-component file, the sampling is ignored);
+ * pixel (y, x) channel c at src + y * row_stride + components * x + c, row_stride >= components * width, any alignment.
+ * width and height 1..65535.  quality 1..100, restart_interval 0..65535 MCUs.
+ *
+ * The seam between the stages is the COEFFICIENT BUFFER of the decoder above (int16, per component [block row][block
+ * column][64], whole-MCU block counts, stored transposed), so what stage 1 writes ppy_jpeg_reconstruct_u8 can read and what
+ * ppy_jpeg_entropy_decode writes stage 2 can code.
+ *
+ * A batch: fill src, row_stride, width, height, components of every descriptor; ppy_jpeg_enc_layout validates them, fills
+ * the rest (geometry; coef_base, ws_base = the image's byte offsets in the batch buffers; scan_capacity) and the four buffer
+ * sizes; ppy_jpeg_enc_pack_table writes the device table (sizes.table_bytes) into host memory; copy it to the device;
+ *   stage 1  ppy_jpeg_enc_coefficients: ONE launch for the whole batch, whatever the number and sizes of the images:
+ *            colour conversion, edge replication, downsampling, forward DCT, quantisation, dummy blocks; integer only;
+ *   stage 2  ppy_jpeg_enc_scan_device: EIGHT launches, no host synchronisation: bits per block | segmented prefix sum per
+ *            image and the restart segments' byte offsets | zero the unstuffed stream | write the bits (OR into zeroed words:
+ *            order-independent, so run-to-run identical) with each segment's 1-bit tail fill | 0xFF count per 64-byte
+ *            chunk | prefix sum per image, length per image | offsets of the images in `out` | stuffed write with RSTn.
+ *            out receives the images' entropy-coded bytes back to back (image i at the sum of the lengths before it, no
+ *            header, no EOI), lengths[i] their sizes.  Every byte of ws it reads it has written in the same call.
+ * CAPACITY: one block codes to at most 22 + 63 * 26 = 1660 bits (DC: 11-bit code + 11; AC: 16-bit code + 10), < 208 bytes,
+ * every byte may be stuffed, and every restart segment adds at most one stuffed fill byte and a 2-byte marker:
+ *   ppy_jpeg_enc_scan_capacity(blocks, segments) = 416 * blocks + 4 * segments.
+ * out_bytes below the sum of the images' capacities is refused on the host (PPY_ERR_WORKSPACE), never overrun.  The device
+ * stage keeps 32-bit positions: an image whose capacity is above 2^29 is PPY_ERR_UNSUPPORTED in ppy_jpeg_enc_scan_device
+ * (the host twin takes it).
+ * ppy_jpeg_enc_scan_host is the host twin of stage 2 for ONE image: plain C++, stateless, no GPU call, any thread; the same
+ * bytes from the same coefficients (h_coef = the image's own coefficients, desc.coef_bytes of them; coef_base is not read).
+ * ppy_jpeg_enc_header writes SOI .. SOS for one image (ppy_jpeg_enc_header_bytes of them); the file is header | scan | FF D9.
+ * ppy_jpeg_enc_quant: the two quantiser tables of a quality, 64 entries each in natural (row-major) order.
+ * TRUST BOUNDARY as for the decoder: parameters and descriptors are validated on the host and size the grids; the kernels
+ * read the device table, source pointers and row strides included, WITHOUT further checks.  The table must be the one
+ * ppy_jpeg_enc_pack_table wrote from these very descriptors.  Bad arguments return PPY_ERR_BAD_ARG, a sampling outside the
+ * three PPY_ERR_UNSUPPORTED; h_reason (NULL or 64 chars) says why. */
+typedef struct ppy_jpeg_enc_params_t {
+    int quality;                      /* 1..100 */
+    int h_samp, v_samp;               /* luma sampling factors: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0) */
+    int restart_interval;             /* MCUs, 0 = none */
+} ppy_jpeg_enc_params_t;
+typedef struct ppy_jpeg_enc_desc_t {
+    const unsigned char *src;         /* CALLER: device image */
+    long long row_stride;             /* CALLER: bytes */
+    int width, height, components;    /* CALLER */
+    int restart_interval;
+    int h_samp[3], v_samp[3];
+    int blocks_w[3], blocks_h[3];     /* 8x8 blocks per row / column of each component, whole MCUs */
+    int real_w[3], real_h[3];         /* of which hold samples: ceil(component size / 8); the others are dummy blocks */
+    int mcus_w, mcus_h;
+    long long blocks, segments;       /* blocks of the image; restart segments (1 without restarts) */
+    long long coef_offset[3];         /* int16 elements from the start of the image's coefficients */
+    long long coef_bytes, coef_base;  /* size, and byte offset in the batch coefficient buffer (% 16 == 0) */
+    long long scan_capacity;          /* ppy_jpeg_enc_scan_capacity(blocks, segments) */
+    long long ws_bytes, ws_base;      /* stage 2 workspace of the image and its byte offset (% 16 == 0) */
+} ppy_jpeg_enc_desc_t;
+typedef struct ppy_jpeg_enc_sizes_t {
+    size_t table_bytes, coef_bytes, ws_bytes, out_bytes;
+} ppy_jpeg_enc_sizes_t;
+int ppy_jpeg_enc_quant(int quality, unsigned short *h_luma, unsigned short *h_chroma);
+size_t ppy_jpeg_enc_header_bytes(int components, int restart_interval);
+int ppy_jpeg_enc_header(const ppy_jpeg_enc_params_t *h_params, int width, int height, int components, unsigned char *h_out,
+                        size_t capacity, size_t *h_used, char *h_reason);
+size_t ppy_jpeg_enc_scan_capacity(long long blocks, long long segments);
+int ppy_jpeg_enc_layout(const ppy_jpeg_enc_params_t *h_params, int n, ppy_jpeg_enc_desc_t *h_descs, ppy_jpeg_enc_sizes_t *h_sizes,
+                        char *h_reason);
+int ppy_jpeg_enc_pack_table(const ppy_jpeg_enc_params_t *h_params, int n, const ppy_jpeg_enc_desc_t *h_descs, void *h_table,
+                            size_t table_bytes);
+int ppy_jpeg_enc_coefficients(int n, const ppy_jpeg_enc_desc_t *h_descs, const void *table, int16_t *coef, size_t coef_bytes,
+                              void *stream);
+int ppy_jpeg_enc_scan_device(int n, const ppy_jpeg_enc_desc_t *h_descs, const void *table, const int16_t *coef, size_t coef_bytes,
+                             unsigned char *out, size_t out_bytes, unsigned long long *lengths, void *ws, size_t ws_bytes,
+                             void *stream);
+int ppy_jpeg_enc_scan_host(const ppy_jpeg_enc_desc_t *h_desc, const int16_t *h_coef, size_t coef_bytes, unsigned char *h_out,
+                           size_t capacity, size_t *h_len, char *h_reason);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('PPYOLO_HIP_LIB') or os.path.join(_HERE, 'lib', 'libppyolo_hip.so')     # (override: experiments)
 
 OK = 0
+ERR_UNSUPPORTED = -2      # PPY_ERR_UNSUPPORTED (include/ppyolo_hip.h)
 ACT = {None: 0, 'relu': 1, 'leaky': 2}
 
 
@@ -55,6 +56,25 @@ class JpegDesc(ctypes.Structure):
     _fields_ = [('width', c_int), ('height', c_int), ('components', c_int), ('orientation', c_int), ('h_samp', c_int * 3),
                 ('v_samp', c_int * 3), ('blocks_w', c_int * 3), ('blocks_h', c_int * 3), ('coef_offset', c_longlong * 3),
                 ('coef_bytes', c_longlong), ('coef_base', c_longlong), ('quant', (ctypes.c_ushort * 64) * 3)]
+
+
+class JpegEncParams(ctypes.Structure):
+    """ppy_jpeg_enc_params_t (include/ppyolo_hip.h)."""
+    _fields_ = [('quality', c_int), ('h_samp', c_int), ('v_samp', c_int), ('restart_interval', c_int)]
+
+
+class JpegEncDesc(ctypes.Structure):
+    """ppy_jpeg_enc_desc_t (include/ppyolo_hip.h)."""
+    _fields_ = [('src', c_void_p), ('row_stride', c_longlong), ('width', c_int), ('height', c_int), ('components', c_int),
+                ('restart_interval', c_int), ('h_samp', c_int * 3), ('v_samp', c_int * 3), ('blocks_w', c_int * 3),
+                ('blocks_h', c_int * 3), ('real_w', c_int * 3), ('real_h', c_int * 3), ('mcus_w', c_int), ('mcus_h', c_int),
+                ('blocks', c_longlong), ('segments', c_longlong), ('coef_offset', c_longlong * 3), ('coef_bytes', c_longlong),
+                ('coef_base', c_longlong), ('scan_capacity', c_longlong), ('ws_bytes', c_longlong), ('ws_base', c_longlong)]
+
+
+class JpegEncSizes(ctypes.Structure):
+    """ppy_jpeg_enc_sizes_t (include/ppyolo_hip.h)."""
+    _fields_ = [('table_bytes', c_size_t), ('coef_bytes', c_size_t), ('ws_bytes', c_size_t), ('out_bytes', c_size_t)]
 
 
 _PROTOS = {
@@ -190,6 +210,16 @@ _PROTOS = {
     'ppy_jpeg_entropy_device': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
     'ppy_jpeg_entropy_twin': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t]),
     'ppy_jpeg_reason_string': (ctypes.c_char_p, [c_int]),
+    'ppy_jpeg_enc_quant': (c_int, [c_int, c_void_p, c_void_p]),
+    'ppy_jpeg_enc_header_bytes': (c_size_t, [c_int, c_int]),
+    'ppy_jpeg_enc_header': (c_int, [ctypes.POINTER(JpegEncParams), c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_void_p]),
+    'ppy_jpeg_enc_scan_capacity': (c_size_t, [c_longlong, c_longlong]),
+    'ppy_jpeg_enc_layout': (c_int, [ctypes.POINTER(JpegEncParams), c_int, ctypes.POINTER(JpegEncDesc), ctypes.POINTER(JpegEncSizes), c_void_p]),
+    'ppy_jpeg_enc_pack_table': (c_int, [ctypes.POINTER(JpegEncParams), c_int, ctypes.POINTER(JpegEncDesc), c_void_p, c_size_t]),
+    'ppy_jpeg_enc_coefficients': (c_int, [c_int, ctypes.POINTER(JpegEncDesc), c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ppy_jpeg_enc_scan_device': (c_int, [c_int, ctypes.POINTER(JpegEncDesc), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                         c_void_p, c_size_t, c_void_p]),
+    'ppy_jpeg_enc_scan_host': (c_int, [ctypes.POINTER(JpegEncDesc), c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_void_p]),
 }
 
 

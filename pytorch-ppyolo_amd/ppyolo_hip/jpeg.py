@@ -15,7 +15,12 @@ data is then found on the device and comes back as one status word per image.  T
 
 Baseline Huffman JPEG only (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0): anything else raises PPYoloHipError naming the reason, so a
 caller can hand that file to a decoder of its own.  A truncated or damaged file is an error too (libjpeg would fill the
-missing part with grey and warn)."""
+missing part with grey and warn).
+
+JpegEncoder is the same codec run the other way: uint8 device images -> the bytes libjpeg-turbo writes with its defaults
+(cv2.imwrite, reference demo.py:50; Pillow's Image.save), byte for byte.  Both stages run on the device
+(csrc/jpeg_encode.hip): pixels -> the coefficient buffer the decoder defines -> entropy-coded bytes; the host writes the
+headers and reads lengths and bytes back (two copies, one stream wait per call)."""
 import ctypes
 import os
 import threading
@@ -300,3 +305,185 @@ class JpegDecoder(object):
 
     def imread(self, path):
         return self.decode([path])[0]
+
+
+# ---- encoding ---------------------------------------------------------------------------------------------------------------
+SUBSAMPLINGS = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
+
+
+def _same_device(a, b):
+    return a.type == b.type and (a.index if a.index is not None else torch.cuda.current_device()) == \
+        (b.index if b.index is not None else torch.cuda.current_device())
+
+
+class EncBatch(object):
+    """Output of stage 1: the descriptors, the device table and the device coefficient buffer (the decoder's layout; image i
+    at descs[i].coef_base), plus the source tensors, which the kernels read in place and which therefore stay referenced."""
+    __slots__ = ('n', 'descs', 'sizes', 'table', 'coef', 'sources')
+
+    def coefficients(self, i):
+        """Image i's coefficients as the seam stores them: one int16 device tensor [block rows, block columns, 64] per
+        component, whole-MCU block counts, TRANSPOSED inside a block (index column * 8 + row)."""
+        d = self.descs[i]
+        flat = self.coef[d.coef_base:d.coef_base + d.coef_bytes].view(torch.int16)
+        return [flat[d.coef_offset[c]:d.coef_offset[c] + d.blocks_w[c] * d.blocks_h[c] * 64].view(d.blocks_h[c], d.blocks_w[c], 64)
+                for c in range(d.components)]
+
+
+class JpegEncoder(object):
+    def __init__(self, quality=95, subsampling='4:2:0', restart_interval=0, entropy='device', device='cuda'):
+        """quality: 1..100 (95 is cv2's default; Pillow's is 75).  subsampling: '4:4:4', '4:2:2' or '4:2:0' (libjpeg's and cv2's
+        default); a grey image ignores it.  restart_interval: MCUs between restart markers, 0 = none.  entropy: 'device' (the
+        bit-packer on the GPU) or 'host' (its host twin: the coefficients are read back instead of the bytes)."""
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+            raise PPYoloHipError('quality must be an integer in 1..100, got %r' % (quality,))
+        if subsampling not in SUBSAMPLINGS:
+            raise PPYoloHipError("subsampling must be one of '4:4:4', '4:2:2', '4:2:0', got %r" % (subsampling,))
+        if isinstance(restart_interval, bool) or not isinstance(restart_interval, int) or not 0 <= restart_interval <= 65535:
+            raise PPYoloHipError('restart_interval must be an integer in 0..65535 MCUs, got %r' % (restart_interval,))
+        if entropy not in ('host', 'device'):
+            raise PPYoloHipError("entropy must be 'host' or 'device', got %r" % (entropy,))
+        self.quality, self.subsampling, self.restart_interval, self.entropy = quality, subsampling, restart_interval, entropy
+        self.device = torch.device(device)
+        h, v = SUBSAMPLINGS[subsampling]
+        self.params = _lib.JpegEncParams(quality, h, v, restart_interval)
+        self._stage = None              # pinned buffer the descriptor table is packed into
+        self._busy = None               # event recorded after the last copy out of it
+
+    # ---- the parts --------------------------------------------------------------------------------------------------------
+    def quant_tables(self):
+        """(luma, chroma): the quantiser tables of this quality, 64 ints each in natural (row-major) order."""
+        a, b = (ctypes.c_ushort * 64)(), (ctypes.c_ushort * 64)()
+        _check(lib().ppy_jpeg_enc_quant(self.quality, a, b), 'ppy_jpeg_enc_quant')
+        return list(a), list(b)
+
+    def header(self, width, height, components=3):
+        """The bytes from SOI through SOS of a width x height file with 3 (YCbCr) or 1 (grey) components."""
+        L = lib()
+        cap = L.ppy_jpeg_enc_header_bytes(components, self.restart_interval)
+        buf, used, reason = ctypes.create_string_buffer(max(cap, 1)), ctypes.c_size_t(), ctypes.create_string_buffer(64)
+        rc = L.ppy_jpeg_enc_header(ctypes.byref(self.params), width, height, components, buf, cap, ctypes.byref(used), reason)
+        if rc != _lib.OK:
+            raise PPYoloHipError('cannot write a JPEG header: %s (code %d)' % (reason.value.decode() or L.ppy_error_string(rc).decode(), rc))
+        return buf.raw[:used.value]
+
+    def _source(self, i, im):
+        """One input -> a device tensor the kernels read in place (augment.source_image's rule): a uint8 tensor on the
+        encoder's device, [h,w,3] with pixel stride 3 and channel stride 1 or [h,w] with pixel stride 1, any row pitch;
+        numpy arrays and CPU tensors of those shapes are uploaded.  Anything else raises: nothing is copied silently."""
+        if not isinstance(im, torch.Tensor):
+            import numpy as np
+            if not isinstance(im, np.ndarray):
+                raise PPYoloHipError('image %d: expected a uint8 tensor or numpy array [h, w, 3] or [h, w], got %s' % (i, type(im).__name__))
+            if im.dtype != np.uint8:
+                raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
+            im = torch.from_numpy(np.ascontiguousarray(im))
+        if im.dtype != torch.uint8:
+            raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
+        if im.dim() not in (2, 3) or (im.dim() == 3 and im.shape[2] != 3):
+            raise PPYoloHipError('image %d: shape %s, expected [h, w, 3] (BGR) or [h, w] (grey)' % (i, tuple(im.shape)))
+        h, w = im.shape[:2]
+        if not (1 <= h <= 65535 and 1 <= w <= 65535):
+            raise PPYoloHipError('image %d: %d x %d, width and height must be in 1..65535' % (i, w, h))
+        if im.device.type == 'cpu':
+            return im.contiguous().to(self.device, non_blocking=False)
+        if not _same_device(im.device, self.device):
+            raise PPYoloHipError('image %d lives on %s, the encoder on %s: move it there (`.to(device)`) or pass a numpy array'
+                                 % (i, im.device, self.device))
+        pix = 3 if im.dim() == 3 else 1
+        if im.stride(1) != pix or (pix == 3 and im.stride(2) != 1) or (h > 1 and im.stride(0) < pix * w):
+            raise PPYoloHipError('image %d: strides %s: a source needs pixel stride %d%s and rows that do not overlap (any row '
+                                 'pitch); call `.contiguous()` on it first' % (i, tuple(im.stride()), pix, ', channel stride 1' if pix == 3 else ''))
+        return im
+
+    def coefficients(self, images):
+        """Stage 1: colour conversion, padding, downsampling, forward DCT and quantisation of the whole batch in one launch on
+        the current stream -> EncBatch."""
+        L = lib()
+        srcs = [self._source(i, im) for i, im in enumerate(images)]
+        n = len(srcs)
+        if n == 0:
+            raise PPYoloHipError('empty batch')
+        descs = (_lib.JpegEncDesc * n)()
+        for d, t in zip(descs, srcs):
+            pix = 3 if t.dim() == 3 else 1
+            d.src, d.row_stride = t.data_ptr(), max(t.stride(0), pix * t.shape[1])
+            d.width, d.height, d.components = t.shape[1], t.shape[0], pix
+        sizes, reason = _lib.JpegEncSizes(), ctypes.create_string_buffer(64)
+        rc = L.ppy_jpeg_enc_layout(ctypes.byref(self.params), n, descs, ctypes.byref(sizes), reason)
+        if rc != _lib.OK:
+            raise PPYoloHipError('cannot encode: %s (code %d)' % (reason.value.decode() or L.ppy_error_string(rc).decode(), rc))
+        if self._busy is not None:              # the last copy out of the staging buffer
+            self._busy.synchronize()
+        if self._stage is None or self._stage.numel() < sizes.table_bytes:
+            t = torch.empty(max(sizes.table_bytes, 1 << 16), dtype=torch.uint8)
+            self._stage = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
+        _check(L.ppy_jpeg_enc_pack_table(ctypes.byref(self.params), n, descs, self._stage.data_ptr(), sizes.table_bytes), 'ppy_jpeg_enc_pack_table')
+        eb = EncBatch()
+        eb.n, eb.descs, eb.sizes, eb.sources = n, descs, sizes, srcs
+        eb.table = torch.empty(sizes.table_bytes, dtype=torch.uint8, device=self.device)
+        eb.table.copy_(self._stage[:sizes.table_bytes], non_blocking=True)
+        self._busy = torch.cuda.Event()
+        self._busy.record()
+        eb.coef = torch.empty(max(sizes.coef_bytes, 16), dtype=torch.uint8, device=self.device)
+        _check(L.ppy_jpeg_enc_coefficients(n, descs, eb.table.data_ptr(), eb.coef.data_ptr(), sizes.coef_bytes,
+                                           torch.cuda.current_stream().cuda_stream), 'ppy_jpeg_enc_coefficients')
+        return eb
+
+    def scan_device(self, eb):
+        """Stage 2 on the device: eight launches on the current stream, nothing read back -> (out, lengths): a uint8 device
+        tensor holding the images' entropy-coded bytes back to back, and their sizes (int64 device tensor [n])."""
+        L = lib()
+        ws = torch.empty(max(eb.sizes.ws_bytes, 16), dtype=torch.uint8, device=self.device)
+        out = torch.empty(max(eb.sizes.out_bytes, 16), dtype=torch.uint8, device=self.device)
+        lengths = torch.empty(eb.n, dtype=torch.int64, device=self.device)
+        rc = L.ppy_jpeg_enc_scan_device(eb.n, eb.descs, eb.table.data_ptr(), eb.coef.data_ptr(), eb.sizes.coef_bytes, out.data_ptr(),
+                                        eb.sizes.out_bytes, lengths.data_ptr(), ws.data_ptr(), eb.sizes.ws_bytes,
+                                        torch.cuda.current_stream().cuda_stream)
+        if rc == _lib.ERR_UNSUPPORTED:
+            raise PPYoloHipError("an image of the batch is too large for the device entropy stage (its capacity bound is over 2^29 "
+                                 "bytes): use JpegEncoder(entropy='host')")
+        _check(rc, 'ppy_jpeg_enc_scan_device')
+        return out, lengths
+
+    def scan_host(self, eb, coef=None):
+        """Stage 2 through the host twin -> list of entropy-coded byte strings.  coef: the host copy of the batch's
+        coefficient buffer (a uint8 CPU tensor); default: eb.coef read back, which waits for the stream."""
+        L = lib()
+        coef = eb.coef.cpu() if coef is None else coef
+        scans = []
+        for i in range(eb.n):
+            d = eb.descs[i]
+            buf, used, reason = ctypes.create_string_buffer(d.scan_capacity), ctypes.c_size_t(), ctypes.create_string_buffer(64)
+            rc = L.ppy_jpeg_enc_scan_host(ctypes.byref(d), coef.data_ptr() + d.coef_base, d.coef_bytes, buf, d.scan_capacity,
+                                          ctypes.byref(used), reason)
+            if rc != _lib.OK:
+                raise PPYoloHipError('image %d: %s (code %d)' % (i, reason.value.decode() or L.ppy_error_string(rc).decode(), rc))
+            scans.append(buf.raw[:used.value])
+        return scans
+
+    # ---- the user's calls -------------------------------------------------------------------------------------------------
+    def encode(self, images):
+        """list of images -> list of bytes, each a complete JPEG file.  Asynchronous on the current stream up to the read-back:
+        two blocking copies, one stream wait -- the lengths (this waits for the stream), then exactly that many bytes, which
+        finds the stream idle.  A numpy or CPU-tensor input adds one blocking upload each; device tensors add none."""
+        eb = self.coefficients(images)
+        if self.entropy == 'device':
+            out, lengths = self.scan_device(eb)
+            lens = lengths.cpu().tolist()
+            data = out[:sum(lens)].cpu().numpy().tobytes()
+            scans, off = [], 0
+            for ln in lens:
+                scans.append(data[off:off + ln])
+                off += ln
+        else:
+            scans = self.scan_host(eb)
+        return [self.header(d.width, d.height, d.components) + s + b'\xff\xd9' for d, s in zip(eb.descs, scans)]
+
+    def imencode(self, img):
+        return self.encode([img])[0]
+
+    def imwrite(self, path, img):
+        data = self.imencode(img)
+        with open(path, 'wb') as fh:
+            fh.write(data)
