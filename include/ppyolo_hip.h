@@ -843,6 +843,47 @@ int ppy_jpeg_enc_scan_device(int n, const ppy_jpeg_enc_desc_t *h_descs, const vo
 int ppy_jpeg_enc_scan_host(const ppy_jpeg_enc_desc_t *h_desc, const int16_t *h_coef, size_t coef_bytes, unsigned char *h_out,
                            size_t capacity, size_t *h_len, char *h_reason);
 
+/* ------------------------------------------------------------------------------------
+ * Drawing detections: the reference's Decode.draw (model/decode_np.py:98-123) on device images, in place, ONE launch per
+ * batch, no host synchronisation, no workspace, no atomics; bit for bit what a sequential painter of the rules below gives,
+ * whatever the scheduling (every pixel is stored by the last row that covers it, and by nobody else).  The rows, their
+ * order, the rounding, the colours, the label string and the placement are the reference's; the GLYPHS are Pillow's built-in
+ * bitmap font (6 x 11 cells), not OpenCV's Hershey font -- cv2.putText is not pinned.  DESIGN.md section 10c.
+ *
+ * Image i: h x w pixels of 3 bytes, pixel (y, x) at base + y * pitch + 3 * x, pitch >= 3 * w, any alignment (a decoder's
+ * output, or a crop of a larger image, drawn where it lies).  h, w in 1..65535.  The colour triple of a class is stored in
+ * memory order (on a BGR image, as cv2 does with the reference's tuples).
+ * dets: device [n][K][6] float32 rows (class, score, x0, y0, x1, y1), count: device [n] int32 -- what forward_padded returns.
+ *   DRAWN  rows r < min(count[i], K) with score >= draw_thresh, 0 <= class < num_classes, 0 <= score <= 1 and all six values
+ *          finite; every other row is skipped.  Rows are drawn in row order, a later row over an earlier one; per row the
+ *          outline, then the label background, then the text.
+ *   CORNERS left = max(0, floor(x0 + 0.5)), top = max(0, floor(y0 + 0.5)), right = min(w, floor(x1 + 0.5)), bottom =
+ *          min(h, floor(y1 + 0.5)); sum and floor in float32, clamped to +-2^30 before the conversion.
+ *   OUTLINE the four edges of the rectangle (left, top) .. (right, bottom), corners inclusive and in either order, one pixel
+ *          thick, class colour, clipped (right == w and bottom == h lie outside).  A flat box is one row, a thin one one column.
+ *   LABEL  name + ": " + d.dd with the digits of rint(float64(score) * 100), ties to even (= '%.2f').  tw = 6 * length,
+ *          th = 11.  Background: filled rectangle (left, top) .. (left + tw, top - th - 3), inclusive, class colour, clipped.
+ *          Text: black, its cell grid's top left corner at (left, top - th - 2), clipped.
+ *   FONT   font: device [95][16] bytes, characters 32..126 (any other is drawn as '?'): gx0 + 1, gy0, gx1 + 1, gy1, 0, then
+ *          the 11 rows of the band, bit c + 1 = column c of the cell, -1 <= c < 6 (ppyolo_hip/label_font.py device_table).
+ *          Glyph i of the string owns [6 i + gx0, 6 i + gx1) x [gy0, gy1); glyphs are pasted in string order, a pixel takes
+ *          the bit of the LAST glyph whose rectangle contains it.  A set bit is black, a clear bit leaves the background.
+ * colors: device [num_classes][3] bytes.  names: device [num_classes][64] character codes, name_len: device [num_classes]
+ * int32; h_name_len: the same lengths on the HOST.  h_images: HOST array of the n descriptors, images: its DEVICE copy.
+ * TRUST BOUNDARY: the host arrays are validated and size the grid; the kernel reads the device copies without further
+ * checks, except that every store is clipped to the descriptor's h x w and a class outside [0, num_classes) reads no table.
+ * K outside 1..1024, num_classes < 1 or a name longer than 64 characters is PPY_ERR_UNSUPPORTED; a null pointer, n outside
+ * 1..65535, an extent outside 1..65535 or a short pitch PPY_ERR_BAD_ARG. */
+typedef struct ppy_draw_image_t {
+    unsigned char *base;
+    long long pitch;                  /* bytes per row */
+    int h, w;
+} ppy_draw_image_t;
+int ppy_draw_detections_u8(int n, const ppy_draw_image_t *h_images, const ppy_draw_image_t *images, const float *dets,
+                           const int *count, int K, float draw_thresh, const unsigned char *colors, int num_classes,
+                           const unsigned char *names, const int *name_len, const int *h_name_len, const unsigned char *font,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

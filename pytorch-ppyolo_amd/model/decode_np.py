@@ -2,7 +2,8 @@
 model boundary: `Decode.predict` (:142-150), `detect_image` (:41-57), `detect_batch`
 (:81-96), and `process_image` (:125-140) -- the cv2 resize / normalise / permute in front of the
 model, here ONE HIP kernel on the device (ppyolo_hip/csrc/preprocess.hip; SURVEY.md section 8f
-rank 1).  Drawing (cv2) is host-side post-processing outside the path and is not provided."""
+rank 1) -- and `draw` (:98-123) as one HIP launch (ppyolo_hip/draw.py): the reference's boxes, colours, label strings and
+placement, with Pillow's bitmap font where the reference calls cv2.putText (cv2's glyphs are not pinned: DESIGN.md 10c)."""
 import numpy as np
 import torch
 
@@ -18,6 +19,8 @@ class Decode(object):
         self.target_size = (cfg.test_cfg if for_test else cfg.eval_cfg)['target_size']
         self._pre = None
         self._jpeg = None
+        self._drawer = None
+        self._encoder = None
 
     def _preprocessor(self):
         if self._pre is None:
@@ -69,16 +72,72 @@ class Decode(object):
             return np.array([]), np.array([]), np.array([])
         return pred[:, 2:], pred[:, 1], pred[:, 0].astype(np.int32)
 
+    def drawer(self):
+        if self._drawer is None:
+            from ppyolo_hip.draw import BoxDrawer
+            self._drawer = BoxDrawer(self.all_classes)
+        return self._drawer
+
+    def draw(self, image, boxes, scores, classes):
+        """Reference :98-123, in place: every row given is drawn, in order.  image: a numpy uint8 [h,w,3] array (uploaded, drawn
+        on the device, copied back into the same array) or a uint8 device tensor (drawn where it lies)."""
+        if isinstance(image, torch.Tensor):
+            return self._draw_tensor(image, boxes, scores, classes)
+        return self.drawer().draw_host(image, boxes, scores, classes)
+
+    def _draw_tensor(self, image, boxes, scores, classes):
+        scores = np.asarray(scores, np.float32).reshape(-1)
+        rows = np.concatenate([np.asarray(classes, np.float32).reshape(-1, 1), scores[:, None],
+                               np.asarray(boxes, np.float32).reshape(-1, 4)], axis=1)
+        for lo in range(0, len(rows), 1024):       # the launch takes 1024 rows; in order on one stream, as draw_host does
+            dets = torch.from_numpy(np.ascontiguousarray(rows[lo:lo + 1024])[None]).to(image.device)
+            count = torch.tensor([dets.shape[1]], dtype=torch.int32, device=image.device)
+            self.drawer()([image], dets, count, 0.0)
+        return image
+
+    def _draw_filtered(self, image, boxes, scores, classes, draw_thresh):
+        if len(scores) > 0:                       # reference :51-56
+            pos = np.where(scores >= draw_thresh)
+            self.draw(image, boxes[pos], scores[pos], classes[pos])
+
     def detect_image(self, image, pimage, im_size, draw_image, draw_thresh=0.0):
-        if draw_image:
-            raise NotImplementedError('drawing (cv2) is host-side post-processing outside the hot path')
         pred = self.predict(pimage, im_size)
         boxes, scores, classes = self._split(pred[0])
+        if draw_image:
+            self._draw_filtered(image, boxes, scores, classes, draw_thresh)
         return image, boxes, scores, classes
 
     def detect_batch(self, batch_img, batch_pimage, batch_im_size, draw_image, draw_thresh=0.0):
-        if draw_image:
-            raise NotImplementedError('drawing (cv2) is host-side post-processing outside the hot path')
         pred = self.predict(batch_pimage, batch_im_size)
         res = [self._split(p) for p in pred]
+        if draw_image:
+            for img, (boxes, scores, classes) in zip(batch_img, res):
+                self._draw_filtered(img, boxes, scores, classes, draw_thresh)
         return (list(batch_img), [r[0] for r in res], [r[1] for r in res], [r[2] for r in res])
+
+    def annotate_files(self, paths_or_bytes, draw_thresh=None, decoder=None, encoder=None):
+        """demo.py's loop from file to annotated file: JPEG paths / byte strings -> (list of JPEG bytes, per image (boxes,
+        scores, classes)).  decode -> preprocess -> forward_padded -> draw -> JpegEncoder.encode, all on the device: no pixel
+        and no score visits the host before the encoder's read-back; the detections are read after it.  draw_thresh: default
+        cfg.test_cfg['draw_thresh'].  decoder / encoder: the caller's JpegDecoder / JpegEncoder; default this object's own
+        (the encoder with cv2.imwrite's defaults, quality 95 and 4:2:0)."""
+        if draw_thresh is None:
+            draw_thresh = self.cfg.test_cfg['draw_thresh']
+        if decoder is None:
+            if self._jpeg is None:
+                from ppyolo_hip.jpeg import JpegDecoder
+                self._jpeg = JpegDecoder()
+            decoder = self._jpeg
+        if encoder is None:
+            if self._encoder is None:
+                from ppyolo_hip.jpeg import JpegEncoder
+                self._encoder = JpegEncoder()
+            encoder = self._encoder
+        images = decoder.decode(list(paths_or_bytes))
+        pimage, im_size = self._preprocessor()(images)
+        dets, count, _ = self._yolo.forward_padded(pimage, im_size)
+        self.drawer()(images, dets, count, draw_thresh)
+        files = encoder.encode(images)
+        dets, count = dets.cpu().numpy(), count.cpu().tolist()
+        empty = (np.array([]), np.array([]), np.array([]))
+        return files, [self._split(d[:c]) if c > 0 else empty for d, c in zip(dets, count)]

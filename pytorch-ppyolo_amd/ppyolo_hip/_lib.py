@@ -77,6 +77,13 @@ class JpegEncSizes(ctypes.Structure):
     _fields_ = [('table_bytes', c_size_t), ('coef_bytes', c_size_t), ('ws_bytes', c_size_t), ('out_bytes', c_size_t)]
 
 
+class DrawImage(ctypes.Structure):
+    """ppy_draw_image_t (include/ppyolo_hip.h)."""
+    _fields_ = [('base', c_void_p), ('pitch', c_longlong), ('h', c_int), ('w', c_int)]
+
+
+DRAW_MAX_ROWS, DRAW_NAME_MAX = 1024, 64      # K and name length ppy_draw_detections_u8 takes (include/ppyolo_hip.h)
+
 _PROTOS = {
     'ppy_version': (c_int, []),
     'ppy_error_string': (ctypes.c_char_p, [c_int]),
@@ -220,6 +227,8 @@ _PROTOS = {
     'ppy_jpeg_enc_scan_device': (c_int, [c_int, ctypes.POINTER(JpegEncDesc), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                          c_void_p, c_size_t, c_void_p]),
     'ppy_jpeg_enc_scan_host': (c_int, [ctypes.POINTER(JpegEncDesc), c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_void_p]),
+    'ppy_draw_detections_u8': (c_int, [c_int, ctypes.POINTER(DrawImage), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int,
+                                       c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p, c_void_p]),
 }
 
 

@@ -751,3 +751,29 @@ def multiclass_nms(boxes, num_classes, cand_key, cand_idx, cand_count, nms_top_k
                ('nms_eta=%r (supported: 1.0, no adaptive threshold)' % (nms_eta,), float(nms_eta) != 1.0)]
         raise _lib.PPYoloHipError('ppy_multiclass_nms_f32: unsupported ' + ', '.join(t for t, b in bad if b))
     check(rc, 'ppy_multiclass_nms_f32')
+
+
+def draw_detections(h_images, images, dets, count, draw_thresh, colors, names, name_len, h_name_len, font):
+    """Decode.draw on the device for a batch (ppyolo_hip.draw.BoxDrawer builds the tables): one launch on the current stream,
+    in place.  h_images: a ctypes array of _lib.DrawImage, images: its device copy (uint8 tensor); dets [N,K,6] float32 and
+    count [N] int32 as forward_padded returns them; colors [C,3] uint8, names [C,64] uint8, name_len [C] int32 and font
+    [95,16] uint8 on the device; h_name_len: the lengths as a ctypes int array."""
+    _dev(images, dets, count, colors, names, name_len, font)
+    N, K, _ = dets.shape
+    C = colors.shape[0]
+    assert len(h_images) == N and images.dtype == torch.uint8 and images.is_contiguous() and images.numel() >= N * ctypes.sizeof(_lib.DrawImage)
+    assert images.data_ptr() % 8 == 0
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.shape[2] == 6
+    assert count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (N,)
+    assert colors.dtype == torch.uint8 and colors.is_contiguous() and tuple(colors.shape) == (C, 3)
+    assert names.dtype == torch.uint8 and names.is_contiguous() and tuple(names.shape) == (C, _lib.DRAW_NAME_MAX)
+    assert name_len.dtype == torch.int32 and name_len.is_contiguous() and tuple(name_len.shape) == (C,) and len(h_name_len) == C
+    assert font.dtype == torch.uint8 and font.is_contiguous() and tuple(font.shape) == (95, 16)
+    rc = lib().ppy_draw_detections_u8(N, h_images, images.data_ptr(), dets.data_ptr(), count.data_ptr(), K, float(draw_thresh),
+                                      colors.data_ptr(), C, names.data_ptr(), name_len.data_ptr(), h_name_len, font.data_ptr(), _stream())
+    if rc == _lib.ERR_UNSUPPORTED:
+        bad = [('%d rows per image (supported: 1..%d)' % (K, _lib.DRAW_MAX_ROWS), not 1 <= K <= _lib.DRAW_MAX_ROWS),
+               ('%d classes (at least 1)' % C, C < 1),
+               ('a class name over %d characters' % _lib.DRAW_NAME_MAX, any(v > _lib.DRAW_NAME_MAX for v in h_name_len))]
+        raise _lib.PPYoloHipError('ppy_draw_detections_u8: unsupported: ' + ', '.join(t for t, b in bad if b))
+    check(rc, 'ppy_draw_detections_u8')
