@@ -648,7 +648,8 @@ int ppy_lane_stream_destroy(void *stream);
  * segments and 0xFF fill bytes.  Everything else that is a valid file -- progressive, arithmetic, lossless, 12-bit, 4
  * components, RGB (Adobe transform 0), other sampling factors, several scans -- returns PPY_ERR_UNSUPPORTED, and a file that
  * is damaged or ends early returns PPY_ERR_CORRUPT (libjpeg would fill the rest with grey and warn); both with a reason
- * string.  No input makes these functions read or write outside the buffers they are given.
+ * string.  No input makes these functions read or write outside the buffers they are given.  Progressive files, several
+ * scans and further luma sampling factors are taken on request: the _ex calls below.
  *
  * The seam between host and device is the COEFFICIENT BUFFER: int16, per component [block row][block column][64], block
  * counts those of whole MCUs, quantised values as coded, stored TRANSPOSED inside a block (index column * 8 + row; the
@@ -681,6 +682,7 @@ typedef struct ppy_jpeg_info_t {
     int restart_interval;             /* MCUs, 0 = none */
     long long coef_bytes;             /* size of the image's coefficients */
     char reason[64];                  /* why status != PPY_OK */
+    int progressive;                  /* 1 for an SOF2 file (only ever under PPY_JPEG_ACCEPT_PROGRESSIVE) */
 } ppy_jpeg_info_t;
 typedef struct ppy_jpeg_desc_t {
     int width, height, components, orientation;
@@ -695,6 +697,27 @@ int ppy_jpeg_info(const unsigned char *h_data, size_t bytes, ppy_jpeg_info_t *h_
 /* h_reason: NULL or 64 chars. */
 int ppy_jpeg_entropy_decode(const unsigned char *h_data, size_t bytes, int16_t *h_coef, size_t coef_bytes,
                             ppy_jpeg_desc_t *h_desc, char *h_reason);
+/* The same two calls under an ACCEPT MASK (0 = exactly the calls above, code for code and reason for reason).  Each bit lifts
+ * one refusal:
+ *   PPY_JPEG_ACCEPT_PROGRESSIVE  SOF2 (progressive, Huffman): DC / AC, first and refinement scans as in libjpeg's jdphuff.c;
+ *   PPY_JPEG_ACCEPT_MULTISCAN    SOF0 / SOF1 files whose components come in several scans, in any grouping and order;
+ *   PPY_JPEG_ACCEPT_SAMPLING     3 components with chroma 1x1 and luma h x v, h, v in 1..4, h * v <= 8 (4:4:0, 4:1:1, 4:1:0, ...).
+ * DHT / DQT / DRI between scans hold for the scans that follow; a component's quantisation table is the one in force when its
+ * first scan starts.  A scan of one component is not interleaved: it covers the blocks that hold image samples, and the MCU
+ * padding of the coefficient buffer stays zero.  A progressive file must have sent every coefficient of every component down
+ * to Al = 0 by EOI, otherwise PPY_ERR_UNSUPPORTED "incomplete progressive scan script" (libjpeg would smooth such a file
+ * between blocks); a sequential file must send every component exactly once.  Scan parameters outside T.81, unknown or
+ * repeated components, missing tables, data that ends early and a missing EOI are PPY_ERR_CORRUPT; more than 256 scans is
+ * PPY_ERR_UNSUPPORTED.  The descriptor, the coefficient buffer and everything after them are unchanged: ppy_jpeg_pack_table
+ * and ppy_jpeg_reconstruct_u8 take the further luma factors (a chroma plane at half height and full width goes through
+ * libjpeg's vertical triangle filter, every other new ratio is replicated), still two launches per batch.
+ * ppy_jpeg_scan_prepare (the device entropy mode) takes no mask and keeps refusing all of these. */
+#define PPY_JPEG_ACCEPT_PROGRESSIVE 1u
+#define PPY_JPEG_ACCEPT_MULTISCAN 2u
+#define PPY_JPEG_ACCEPT_SAMPLING 4u
+int ppy_jpeg_info_ex(const unsigned char *h_data, size_t bytes, unsigned accept, ppy_jpeg_info_t *h_info);
+int ppy_jpeg_entropy_decode_ex(const unsigned char *h_data, size_t bytes, unsigned accept, int16_t *h_coef, size_t coef_bytes,
+                               ppy_jpeg_desc_t *h_desc, char *h_reason);
 size_t ppy_jpeg_workspace_bytes(int n, const ppy_jpeg_desc_t *h_descs);
 size_t ppy_jpeg_table_bytes(int n);
 int ppy_jpeg_pack_table(int n, const ppy_jpeg_desc_t *h_descs, unsigned char *const *h_out, const long long *h_row_stride,

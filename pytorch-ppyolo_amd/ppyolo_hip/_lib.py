@@ -36,7 +36,10 @@ class JpegInfo(ctypes.Structure):
     _fields_ = [('status', c_int), ('width', c_int), ('height', c_int), ('out_width', c_int), ('out_height', c_int),
                 ('orientation', c_int), ('components', c_int), ('h_samp', c_int * 3), ('v_samp', c_int * 3),
                 ('blocks_w', c_int * 3), ('blocks_h', c_int * 3), ('restart_interval', c_int), ('coef_bytes', c_longlong),
-                ('reason', ctypes.c_char * 64)]
+                ('reason', ctypes.c_char * 64), ('progressive', c_int)]
+
+
+JPEG_ACCEPT = {'progressive': 1, 'multiscan': 2, 'sampling': 4}      # PPY_JPEG_ACCEPT_* (include/ppyolo_hip.h)
 
 
 class JpegScan(ctypes.Structure):
@@ -204,6 +207,8 @@ _PROTOS = {
     'ppy_lane_stream_destroy': (c_int, [c_void_p]),
     'ppy_jpeg_info': (c_int, [c_void_p, c_size_t, ctypes.POINTER(JpegInfo)]),
     'ppy_jpeg_entropy_decode': (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(JpegDesc), c_void_p]),
+    'ppy_jpeg_info_ex': (c_int, [c_void_p, c_size_t, ctypes.c_uint, ctypes.POINTER(JpegInfo)]),
+    'ppy_jpeg_entropy_decode_ex': (c_int, [c_void_p, c_size_t, ctypes.c_uint, c_void_p, c_size_t, ctypes.POINTER(JpegDesc), c_void_p]),
     'ppy_jpeg_workspace_bytes': (c_size_t, [c_int, ctypes.POINTER(JpegDesc)]),
     'ppy_jpeg_table_bytes': (c_size_t, [c_int]),
     'ppy_jpeg_pack_table': (c_int, [c_int, ctypes.POINTER(JpegDesc), ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_int,

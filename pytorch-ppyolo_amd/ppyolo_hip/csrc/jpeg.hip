@@ -57,6 +57,8 @@ struct Parsed {
     unsigned short q[4][64];                         // zigzag order, as in the file
     HuffTab dc[4], ac[4];
     size_t data;                                     // offset of the entropy-coded data
+    bool full, progressive;                          // read by the scan loop (decode_full), which latches the tables in ql
+    unsigned short ql[3][64];                        // per component: the table in force when its first scan started
 };
 
 struct Fail {
@@ -118,13 +120,100 @@ int exif_orientation(const unsigned char *s, size_t n) {      // payload of an A
     return 1;
 }
 
+struct Markers {      // what the segments before a scan leave behind, besides the tables in Parsed
+    bool sof, jfif, have_orient;
+    int adobe;
+};
+
+// The SOF segment of a Huffman-coded DCT frame (SOF0, SOF1, SOF2): payload s of sl bytes.
+int frame_segment(const unsigned char *s, size_t sl, Parsed &P, Markers &M, Fail &f) {
+    if (M.sof || sl < 6) return fail(f, PPY_ERR_CORRUPT, "bad SOF segment");
+    const int prec = s[0], nc = s[5];
+    P.H = s[1] << 8 | s[2];
+    P.W = s[3] << 8 | s[4];
+    if (sl < 6 + 3 * (size_t)nc) return fail(f, PPY_ERR_CORRUPT, "bad SOF segment");
+    if (prec != 8) return fail(f, PPY_ERR_UNSUPPORTED, "sample precision other than 8 bits");
+    if (P.H == 0 || P.W == 0) return fail(f, PPY_ERR_UNSUPPORTED, "zero image size (DNL)");
+    if (nc != 1 && nc != 3) return fail(f, PPY_ERR_UNSUPPORTED, "component count other than 1 or 3");
+    P.ncomp = nc;
+    for (int k = 0; k < nc; ++k) {
+        P.id[k] = s[6 + 3 * k];
+        P.h[k] = s[7 + 3 * k] >> 4;
+        P.v[k] = s[7 + 3 * k] & 15;
+        P.tq[k] = s[8 + 3 * k];
+    }
+    M.sof = true;
+    return PPY_OK;
+}
+
+// Every segment but SOF0-2 and SOS: the tables (DQT, DHT, DRI; they hold for whatever scan follows), the APPn segments that
+// are read, the frame types that are refused.  Anything else is skipped.
+int table_segment(int m, const unsigned char *s, size_t sl, Parsed &P, Markers &M, Fail &f) {
+    if (m == 0xDB) {
+        size_t j = 0;
+        while (j < sl) {
+            const int pq = s[j] >> 4, tq = s[j] & 15;
+            ++j;
+            if (pq > 1 || tq > 3 || j + 64 * (size_t)(pq + 1) > sl) return fail(f, PPY_ERR_CORRUPT, "bad DQT segment");
+            for (int k = 0; k < 64; ++k) P.q[tq][k] = pq ? (unsigned short)(s[j + 2 * k] << 8 | s[j + 2 * k + 1]) : s[j + k];
+            P.qdef[tq] = true;
+            j += 64 * (size_t)(pq + 1);
+        }
+    } else if (m >= 0xC9 && m <= 0xCF) {      // SOF9-15 and DAC
+        return fail(f, PPY_ERR_UNSUPPORTED, "arithmetic coding");
+    } else if (m == 0xC3 || (m >= 0xC5 && m <= 0xC7)) {
+        return fail(f, PPY_ERR_UNSUPPORTED, "lossless or hierarchical JPEG");
+    } else if (m == 0xC4) {
+        size_t j = 0;
+        while (j < sl) {
+            if (j + 17 > sl) return fail(f, PPY_ERR_CORRUPT, "bad DHT segment");
+            const int tc = s[j] >> 4, th = s[j] & 15;
+            int total = 0;
+            for (int k = 0; k < 16; ++k) total += s[j + 1 + k];
+            if (tc > 1 || th > 3 || total > 256 || j + 17 + (size_t)total > sl) return fail(f, PPY_ERR_CORRUPT, "bad DHT segment");
+            if (!build_huff(tc ? P.ac[th] : P.dc[th], s + j + 1, s + j + 17, total))
+                return fail(f, PPY_ERR_CORRUPT, "bad Huffman table");
+            j += 17 + (size_t)total;
+        }
+    } else if (m == 0xDD) {
+        if (sl < 2) return fail(f, PPY_ERR_CORRUPT, "bad DRI segment");
+        P.dri = s[0] << 8 | s[1];
+    } else if (m == 0xE0 && sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) {
+        M.jfif = true;
+    } else if (m == 0xE1 && !M.have_orient && sl >= 6 && memcmp(s, "Exif\0\0", 6) == 0) {
+        P.orientation = exif_orientation(s, sl);
+        M.have_orient = true;
+    } else if (m == 0xEE && sl >= 12 && memcmp(s, "Adobe", 5) == 0) {
+        M.adobe = s[11];
+    }
+    return PPY_OK;
+}
+
+bool rgb_file(const Parsed &P, const Markers &M) {
+    return M.adobe == 0 || (M.adobe < 0 && !M.jfif && P.id[0] == 'R' && P.id[1] == 'G' && P.id[2] == 'B');
+}
+
+void frame_geometry(Parsed &P) {      // from the sampling factors: MCU counts and the layout of the coefficient buffer
+    P.hmax = P.h[0];
+    P.vmax = P.v[0];
+    P.mcux = (P.W + 8 * P.hmax - 1) / (8 * P.hmax);
+    P.mcuy = (P.H + 8 * P.vmax - 1) / (8 * P.vmax);
+    long long off = 0;
+    for (int k = 0; k < P.ncomp; ++k) {
+        P.bw[k] = P.mcux * P.h[k];
+        P.bh[k] = P.mcuy * P.v[k];
+        P.coef_off[k] = off;
+        off += (long long)P.bw[k] * P.bh[k] * 64;
+    }
+    P.coef_elems = off;
+}
+
 // Markers up to and including SOS.  Every read is bounds-checked against n.
 int parse(const unsigned char *d, size_t n, Parsed &P, Fail &f) {
     memset(&P, 0, sizeof(P));
     if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(f, PPY_ERR_CORRUPT, "no SOI marker");
     size_t i = 2;
-    bool sof = false, jfif = false, have_orient = false;
-    int adobe = -1;
+    Markers M = {false, false, false, -1};
     P.orientation = 1;
     for (;;) {
         if (i + 2 > n || d[i] != 0xFF) return fail(f, PPY_ERR_CORRUPT, "marker expected");
@@ -142,63 +231,14 @@ int parse(const unsigned char *d, size_t n, Parsed &P, Fail &f) {
         const unsigned char *s = d + i + 2;
         const size_t sl = L - 2;
         i += L;
-        if (m == 0xDB) {
-            size_t j = 0;
-            while (j < sl) {
-                const int pq = s[j] >> 4, tq = s[j] & 15;
-                ++j;
-                if (pq > 1 || tq > 3 || j + 64 * (size_t)(pq + 1) > sl) return fail(f, PPY_ERR_CORRUPT, "bad DQT segment");
-                for (int k = 0; k < 64; ++k) P.q[tq][k] = pq ? (unsigned short)(s[j + 2 * k] << 8 | s[j + 2 * k + 1]) : s[j + k];
-                P.qdef[tq] = true;
-                j += 64 * (size_t)(pq + 1);
-            }
-        } else if (m == 0xC0 || m == 0xC1) {
-            if (sof || sl < 6) return fail(f, PPY_ERR_CORRUPT, "bad SOF segment");
-            const int prec = s[0], nc = s[5];
-            P.H = s[1] << 8 | s[2];
-            P.W = s[3] << 8 | s[4];
-            if (sl < 6 + 3 * (size_t)nc) return fail(f, PPY_ERR_CORRUPT, "bad SOF segment");
-            if (prec != 8) return fail(f, PPY_ERR_UNSUPPORTED, "sample precision other than 8 bits");
-            if (P.H == 0 || P.W == 0) return fail(f, PPY_ERR_UNSUPPORTED, "zero image size (DNL)");
-            if (nc != 1 && nc != 3) return fail(f, PPY_ERR_UNSUPPORTED, "component count other than 1 or 3");
-            P.ncomp = nc;
-            for (int k = 0; k < nc; ++k) {
-                P.id[k] = s[6 + 3 * k];
-                P.h[k] = s[7 + 3 * k] >> 4;
-                P.v[k] = s[7 + 3 * k] & 15;
-                P.tq[k] = s[8 + 3 * k];
-            }
-            sof = true;
+        if (m == 0xC0 || m == 0xC1) {
+            if (frame_segment(s, sl, P, M, f) != PPY_OK) return f.code;
         } else if (m == 0xC2) {
             return fail(f, PPY_ERR_UNSUPPORTED, "progressive JPEG");
-        } else if (m >= 0xC9 && m <= 0xCF) {      // SOF9-15 and DAC
-            return fail(f, PPY_ERR_UNSUPPORTED, "arithmetic coding");
-        } else if (m == 0xC3 || (m >= 0xC5 && m <= 0xC7)) {
-            return fail(f, PPY_ERR_UNSUPPORTED, "lossless or hierarchical JPEG");
-        } else if (m == 0xC4) {
-            size_t j = 0;
-            while (j < sl) {
-                if (j + 17 > sl) return fail(f, PPY_ERR_CORRUPT, "bad DHT segment");
-                const int tc = s[j] >> 4, th = s[j] & 15;
-                int total = 0;
-                for (int k = 0; k < 16; ++k) total += s[j + 1 + k];
-                if (tc > 1 || th > 3 || total > 256 || j + 17 + (size_t)total > sl) return fail(f, PPY_ERR_CORRUPT, "bad DHT segment");
-                if (!build_huff(tc ? P.ac[th] : P.dc[th], s + j + 1, s + j + 17, total))
-                    return fail(f, PPY_ERR_CORRUPT, "bad Huffman table");
-                j += 17 + (size_t)total;
-            }
-        } else if (m == 0xDD) {
-            if (sl < 2) return fail(f, PPY_ERR_CORRUPT, "bad DRI segment");
-            P.dri = s[0] << 8 | s[1];
-        } else if (m == 0xE0 && sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) {
-            jfif = true;
-        } else if (m == 0xE1 && !have_orient && sl >= 6 && memcmp(s, "Exif\0\0", 6) == 0) {
-            P.orientation = exif_orientation(s, sl);
-            have_orient = true;
-        } else if (m == 0xEE && sl >= 12 && memcmp(s, "Adobe", 5) == 0) {
-            adobe = s[11];
-        } else if (m == 0xDA) {
-            if (!sof) return fail(f, PPY_ERR_CORRUPT, "SOS before SOF");
+        } else if (m != 0xDA) {
+            if (table_segment(m, s, sl, P, M, f) != PPY_OK) return f.code;
+        } else {
+            if (!M.sof) return fail(f, PPY_ERR_CORRUPT, "SOS before SOF");
             if (sl < 1 || sl < 4 + 2 * (size_t)s[0]) return fail(f, PPY_ERR_CORRUPT, "bad SOS segment");
             if (s[0] != P.ncomp) return fail(f, PPY_ERR_UNSUPPORTED, "multiple scans");
             for (int k = 0; k < P.ncomp; ++k) {
@@ -207,8 +247,7 @@ int parse(const unsigned char *d, size_t n, Parsed &P, Fail &f) {
                 P.ta[k] = s[2 + 2 * k] & 15;
             }
             if (P.ncomp == 3) {
-                if (adobe == 0 || (adobe < 0 && !jfif && P.id[0] == 'R' && P.id[1] == 'G' && P.id[2] == 'B'))
-                    return fail(f, PPY_ERR_UNSUPPORTED, "RGB colour space (Adobe transform 0)");
+                if (rgb_file(P, M)) return fail(f, PPY_ERR_UNSUPPORTED, "RGB colour space (Adobe transform 0)");
                 const bool luma = (P.h[0] == 1 && P.v[0] == 1) || (P.h[0] == 2 && P.v[0] == 1) || (P.h[0] == 2 && P.v[0] == 2);
                 if (P.h[1] != 1 || P.v[1] != 1 || P.h[2] != 1 || P.v[2] != 1 || !luma)
                     return fail(f, PPY_ERR_UNSUPPORTED, "sampling factors other than 4:4:4, 4:2:2, 4:2:0");
@@ -219,18 +258,7 @@ int parse(const unsigned char *d, size_t n, Parsed &P, Fail &f) {
             for (int k = 0; k < P.ncomp; ++k)
                 if (P.tq[k] > 3 || !P.qdef[P.tq[k]] || P.td[k] > 3 || P.ta[k] > 3 || !P.dc[P.td[k]].defined || !P.ac[P.ta[k]].defined)
                     return fail(f, PPY_ERR_CORRUPT, "scan refers to a missing table");
-            P.hmax = P.h[0];
-            P.vmax = P.v[0];
-            P.mcux = (P.W + 8 * P.hmax - 1) / (8 * P.hmax);
-            P.mcuy = (P.H + 8 * P.vmax - 1) / (8 * P.vmax);
-            long long off = 0;
-            for (int k = 0; k < P.ncomp; ++k) {
-                P.bw[k] = P.mcux * P.h[k];
-                P.bh[k] = P.mcuy * P.v[k];
-                P.coef_off[k] = off;
-                off += (long long)P.bw[k] * P.bh[k] * 64;
-            }
-            P.coef_elems = off;
+            frame_geometry(P);
             P.data = i;
             return PPY_OK;
         }
@@ -293,6 +321,35 @@ inline int decode_symbol(BitReader &br, const HuffTab &t) {
 
 inline int extend(unsigned x, int s) { return x < (1u << (s - 1)) ? (int)x - (1 << s) + 1 : (int)x; }
 
+// One block of a sequential scan; the reason of PPY_ERR_CORRUPT, or nullptr.
+inline const char *seq_block(BitReader &br, const HuffTab &dc, const HuffTab &ac, unsigned &pred, int16_t *blk, const int *stored) {
+    br.fill();
+    const int t = decode_symbol(br, dc);
+    if (t < 0 || t > 15) return "bad Huffman code in the entropy data";
+    if (t) {
+        pred += (unsigned)extend(br.peek(t), t);
+        br.skip(t);
+    }
+    blk[0] = (int16_t)pred;
+    for (int k = 1; k < 64;) {
+        if (br.cnt < 32) br.fill();
+        const int rs = decode_symbol(br, ac);
+        if (rs < 0) return "bad Huffman code in the entropy data";
+        const int r = rs >> 4, s = rs & 15;
+        if (s == 0) {
+            if (r != 15) break;
+            k += 16;
+            continue;
+        }
+        k += r;
+        if (k > 63) return "coefficient index past 63";
+        blk[stored[k]] = (int16_t)extend(br.peek(s), s);
+        br.skip(s);
+        ++k;
+    }
+    return br.overrun() ? "entropy data ends early" : nullptr;
+}
+
 int entropy_decode(const unsigned char *d, size_t n, const Parsed &P, int16_t *coef, Fail &f) {
     BitReader br;
     br.d = d;
@@ -318,36 +375,308 @@ int entropy_decode(const unsigned char *d, size_t n, const Parsed &P, int16_t *c
                 for (int v = 0; v < P.v[c]; ++v) {
                     for (int h = 0; h < P.h[c]; ++h) {
                         int16_t *blk = coef + P.coef_off[c] + ((long long)(my * P.v[c] + v) * P.bw[c] + (mx * P.h[c] + h)) * 64;
-                        br.fill();
-                        const int t = decode_symbol(br, dc);
-                        if (t < 0 || t > 15) return fail(f, PPY_ERR_CORRUPT, "bad Huffman code in the entropy data");
-                        if (t) {
-                            pred[c] += (unsigned)extend(br.peek(t), t);
-                            br.skip(t);
-                        }
-                        blk[0] = (int16_t)pred[c];
-                        for (int k = 1; k < 64;) {
-                            if (br.cnt < 32) br.fill();
-                            const int rs = decode_symbol(br, ac);
-                            if (rs < 0) return fail(f, PPY_ERR_CORRUPT, "bad Huffman code in the entropy data");
-                            const int r = rs >> 4, s = rs & 15;
-                            if (s == 0) {
-                                if (r != 15) break;
-                                k += 16;
-                                continue;
-                            }
-                            k += r;
-                            if (k > 63) return fail(f, PPY_ERR_CORRUPT, "coefficient index past 63");
-                            blk[stored[k]] = (int16_t)extend(br.peek(s), s);
-                            br.skip(s);
-                            ++k;
-                        }
-                        if (br.overrun()) return fail(f, PPY_ERR_CORRUPT, "entropy data ends early");
+                        if (const char *why = seq_block(br, dc, ac, pred[c], blk, stored)) return fail(f, PPY_ERR_CORRUPT, why);
                     }
                 }
             }
         }
     }
+    return PPY_OK;
+}
+
+// ------------------------------------------------------------------------------------------- the scan loop (accept != 0)
+// Frames whose coefficients arrive in more than one scan -- progressive (jdphuff.c) and sequential multi-scan -- and the
+// further luma sampling factors.  The coefficient buffer is the one of the single-scan path; a scan of one component is not
+// interleaved and covers the blocks that hold image samples only, so the MCU padding of the buffer stays zero there.
+struct Scan {
+    int ns, c[3], td[3], ta[3];      // c: component INDEX in the frame
+    int ss, se, ah, al;
+};
+
+inline const char *dc_first(BitReader &br, const HuffTab &dc, unsigned &pred, int al, int16_t *blk) {
+    br.fill();
+    const int t = decode_symbol(br, dc);
+    if (t < 0 || t > 15) return "bad Huffman code in the entropy data";
+    if (t) {
+        pred += (unsigned)extend(br.peek(t), t);
+        br.skip(t);
+    }
+    blk[0] = (int16_t)(pred << al);
+    return nullptr;
+}
+
+inline unsigned one_bit(BitReader &br) {
+    if (br.cnt < 32) br.fill();
+    const unsigned b = br.peek(1);
+    br.skip(1);
+    return b;
+}
+
+// The run length an EOBn symbol announces, less the block it ends.
+inline int eob_run(BitReader &br, int r) {
+    int run = 1 << r;
+    if (r) {
+        if (br.cnt < 32) br.fill();
+        run += (int)br.peek(r);
+        br.skip(r);
+    }
+    return run - 1;
+}
+
+inline const char *ac_first(BitReader &br, const HuffTab &ac, const Scan &S, int &eobrun, int16_t *blk, const int *stored) {
+    if (eobrun > 0) {
+        --eobrun;
+        return nullptr;
+    }
+    for (int k = S.ss; k <= S.se; ++k) {
+        if (br.cnt < 32) br.fill();
+        const int rs = decode_symbol(br, ac);
+        if (rs < 0) return "bad Huffman code in the entropy data";
+        const int r = rs >> 4, s = rs & 15;
+        if (s) {
+            k += r;
+            if (k > S.se) return "coefficient index past the end of the band";
+            blk[stored[k]] = (int16_t)((unsigned)extend(br.peek(s), s) << S.al);
+            br.skip(s);
+        } else if (r == 15) {
+            k += 15;
+        } else {
+            eobrun = eob_run(br, r);
+            break;
+        }
+    }
+    return nullptr;
+}
+
+// jdphuff.c decode_mcu_AC_refine: a new coefficient is +-1 << Al and lands after r still-zero positions; every coefficient
+// that is already nonzero and is passed on the way takes one correction bit.
+inline const char *ac_refine(BitReader &br, const HuffTab &ac, const Scan &S, int &eobrun, int16_t *blk, const int *stored) {
+    const int p1 = 1 << S.al, m1 = -p1;
+    auto correct = [&](int16_t &co) {
+        if (one_bit(br) && (co & p1) == 0) co = (int16_t)(co + (co >= 0 ? p1 : m1));
+    };
+    int k = S.ss;
+    if (eobrun == 0) {
+        for (; k <= S.se; ++k) {
+            if (br.cnt < 32) br.fill();
+            const int rs = decode_symbol(br, ac);
+            if (rs < 0) return "bad Huffman code in the entropy data";
+            int r = rs >> 4, val = 0;
+            const int s = rs & 15;
+            if (s) {
+                if (s != 1) return "bad value in a refinement scan";
+                val = one_bit(br) ? p1 : m1;
+            } else if (r != 15) {
+                eobrun = eob_run(br, r) + 1;      // this block is still to be finished below
+                break;
+            }
+            do {
+                int16_t &co = blk[stored[k]];
+                if (co != 0) correct(co);
+                else if (--r < 0) break;
+                ++k;
+            } while (k <= S.se);
+            if (val) {
+                if (k > S.se) return "coefficient index past the end of the band";
+                blk[stored[k]] = (int16_t)val;
+            }
+        }
+    }
+    if (eobrun > 0) {
+        for (; k <= S.se; ++k)
+            if (blk[stored[k]] != 0) correct(blk[stored[k]]);
+        --eobrun;
+    }
+    return nullptr;
+}
+
+// The entropy-coded data of one scan, from pos to the marker that ends it (pos on return).
+int run_scan(const unsigned char *d, size_t n, const Parsed &P, const Scan &S, int16_t *coef, size_t &pos, Fail &f) {
+    BitReader br;
+    br.d = d;
+    br.n = n;
+    br.reset(pos);
+    int stored[64];
+    for (int k = 0; k < 64; ++k) stored[k] = stored_index(k);
+    const bool inter = S.ns > 1;
+    const int c0 = S.c[0];
+    // units: MCUs of an interleaved scan, otherwise the blocks of the one component that hold image samples
+    const int ux = inter ? P.mcux : ((P.W * P.h[c0] + P.hmax - 1) / P.hmax + 7) / 8;
+    const int uy = inter ? P.mcuy : ((P.H * P.v[c0] + P.vmax - 1) / P.vmax + 7) / 8;
+    const int kind = !P.progressive ? 0 : S.ss == 0 ? (S.ah ? 2 : 1) : (S.ah ? 4 : 3);
+    unsigned pred[3] = {0, 0, 0};
+    int eobrun = 0;
+    long long unit = 0;
+    for (int y = 0; y < uy; ++y) {
+        for (int x = 0; x < ux; ++x, ++unit) {
+            if (P.dri && unit && unit % P.dri == 0) {      // RSTn counts from 0 in every scan
+                if (br.overrun() || br.cnt - br.phantom >= 8) return fail(f, PPY_ERR_CORRUPT, "restart marker expected");
+                size_t p = br.p;
+                while (p + 1 < n && d[p] == 0xFF && d[p + 1] == 0xFF) ++p;
+                if (p + 1 >= n || d[p] != 0xFF || d[p + 1] != 0xD0 + (int)((unit / P.dri - 1) & 7))
+                    return fail(f, PPY_ERR_CORRUPT, "restart marker expected");
+                br.reset(p + 2);
+                pred[0] = pred[1] = pred[2] = 0;
+                eobrun = 0;
+            }
+            for (int k = 0; k < S.ns; ++k) {
+                const int c = S.c[k], nh = inter ? P.h[c] : 1, nv = inter ? P.v[c] : 1;
+                for (int v = 0; v < nv; ++v) {
+                    for (int h = 0; h < nh; ++h) {
+                        int16_t *blk = coef + P.coef_off[c] + ((long long)(y * nv + v) * P.bw[c] + (x * nh + h)) * 64;
+                        const char *why = nullptr;
+                        switch (kind) {
+                            case 0: why = seq_block(br, P.dc[S.td[k]], P.ac[S.ta[k]], pred[k], blk, stored); break;
+                            case 1: why = dc_first(br, P.dc[S.td[k]], pred[k], S.al, blk); break;
+                            case 2: if (one_bit(br)) blk[0] = (int16_t)(blk[0] | 1 << S.al); break;
+                            case 3: why = ac_first(br, P.ac[S.ta[k]], S, eobrun, blk, stored); break;
+                            default: why = ac_refine(br, P.ac[S.ta[k]], S, eobrun, blk, stored); break;
+                        }
+                        if (!why && br.overrun()) why = "entropy data ends early";
+                        if (why) return fail(f, PPY_ERR_CORRUPT, why);
+                    }
+                }
+            }
+        }
+    }
+    pos = br.p;
+    return PPY_OK;
+}
+
+// The SOS payload -> Scan, checked against the frame, the tables in force and the progression so far (bits: per component
+// and coefficient -1 = never sent, else the Al it was last sent with: libjpeg's coef_bits).
+int scan_header(const unsigned char *s, size_t sl, unsigned accept, const Parsed &P, const signed char bits[3][64], const bool *latched,
+                Scan &S, Fail &f) {
+    if (sl < 1 || sl < 4 + 2 * (size_t)s[0]) return fail(f, PPY_ERR_CORRUPT, "bad SOS segment");
+    S.ns = s[0];
+    if (!P.progressive && !(accept & PPY_JPEG_ACCEPT_MULTISCAN)) {
+        if (S.ns != P.ncomp) return fail(f, PPY_ERR_UNSUPPORTED, "multiple scans");
+        for (int k = 0; k < P.ncomp; ++k)
+            if (s[1 + 2 * k] != P.id[k]) return fail(f, PPY_ERR_UNSUPPORTED, "scan component order");
+    }
+    if (S.ns < 1 || S.ns > P.ncomp) return fail(f, PPY_ERR_CORRUPT, "bad SOS segment");
+    int mcu_blocks = 0;
+    for (int k = 0; k < S.ns; ++k) {
+        int c = 0;
+        while (c < P.ncomp && P.id[c] != s[1 + 2 * k]) ++c;
+        if (c == P.ncomp) return fail(f, PPY_ERR_CORRUPT, "scan names an unknown component");
+        for (int j = 0; j < k; ++j)
+            if (S.c[j] == c) return fail(f, PPY_ERR_CORRUPT, "scan names a component twice");
+        S.c[k] = c;
+        S.td[k] = s[2 + 2 * k] >> 4;
+        S.ta[k] = s[2 + 2 * k] & 15;
+        mcu_blocks += P.h[c] * P.v[c];
+    }
+    if (S.ns > 1 && mcu_blocks > 10) return fail(f, PPY_ERR_CORRUPT, "more than 10 blocks in an MCU");
+    const unsigned char *t = s + 1 + 2 * S.ns;
+    S.ss = t[0];
+    S.se = t[1];
+    S.ah = t[2] >> 4;
+    S.al = t[2] & 15;
+    bool need_dc = true, need_ac = true;
+    if (P.progressive) {
+        if (S.ss > 63 || S.se > 63 || S.se < S.ss || S.ah > 13 || S.al > 13) return fail(f, PPY_ERR_CORRUPT, "scan parameters out of range");
+        if (S.ss == 0 && S.se != 0) return fail(f, PPY_ERR_CORRUPT, "DC scan with Se != 0");
+        if (S.ss != 0 && S.ns != 1) return fail(f, PPY_ERR_CORRUPT, "AC scan with more than one component");
+        if (S.ah != 0 && S.ah != S.al + 1) return fail(f, PPY_ERR_CORRUPT, "refinement scan with Ah != Al + 1");
+        need_dc = S.ss == 0 && S.ah == 0;
+        need_ac = S.ss != 0;
+    } else {      // a sequential scan carries whole blocks whatever it says
+        S.ss = 0;
+        S.se = 63;
+        S.ah = S.al = 0;
+    }
+    for (int k = 0; k < S.ns; ++k) {
+        const int c = S.c[k];
+        if (!latched[c] && (P.tq[c] > 3 || !P.qdef[P.tq[c]]))      // its first scan latches the quantisation table
+            return fail(f, PPY_ERR_CORRUPT, "scan refers to a missing table");
+        if ((need_dc && (S.td[k] > 3 || !P.dc[S.td[k]].defined)) || (need_ac && (S.ta[k] > 3 || !P.ac[S.ta[k]].defined)))
+            return fail(f, PPY_ERR_CORRUPT, "scan refers to a missing table");
+        for (int j = S.ss; j <= S.se; ++j) {
+            if (!P.progressive && bits[c][j] >= 0) return fail(f, PPY_ERR_CORRUPT, "scan repeats a component");
+            if (P.progressive && S.ah != (bits[c][j] < 0 ? 0 : bits[c][j])) return fail(f, PPY_ERR_CORRUPT, "scan out of progression order");
+        }
+    }
+    return PPY_OK;
+}
+
+// The whole file under an accept mask.  coef == nullptr: the header pass -- it returns at the first SOS, frame and first
+// scan header checked, P filled as parse() fills it.  Otherwise every scan up to EOI is decoded into coef, which the caller
+// has zeroed, and the completeness rule is applied.
+int decode_full(const unsigned char *d, size_t n, unsigned accept, Parsed &P, int16_t *coef, Fail &f) {
+    memset(&P, 0, sizeof(P));
+    if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(f, PPY_ERR_CORRUPT, "no SOI marker");
+    size_t i = 2;
+    Markers M = {false, false, false, -1};
+    P.orientation = 1;
+    P.full = true;
+    signed char bits[3][64];
+    bool latched[3] = {false, false, false};
+    memset(bits, -1, sizeof(bits));
+    int scans = 0;
+    for (;;) {
+        if (i + 2 > n || d[i] != 0xFF) return fail(f, PPY_ERR_CORRUPT, scans ? "marker expected after a scan (no EOI)" : "marker expected");
+        const int m = d[i + 1];
+        i += 2;
+        if (m == 0xFF) {      // fill byte
+            i -= 1;
+            continue;
+        }
+        if (m == 0x01 || (m >= 0xD0 && m <= 0xD7)) continue;
+        if (m == 0xD9 && scans) break;
+        if (m == 0xD9 || m == 0xD8 || m == 0) return fail(f, PPY_ERR_CORRUPT, scans ? "unexpected marker between scans" : "unexpected marker before the scan");
+        if (i + 2 > n) return fail(f, PPY_ERR_CORRUPT, "truncated segment");
+        const size_t L = (size_t)d[i] << 8 | d[i + 1];
+        if (L < 2 || i + L > n) return fail(f, PPY_ERR_CORRUPT, "truncated segment");
+        const unsigned char *s = d + i + 2;
+        const size_t sl = L - 2;
+        i += L;
+        if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
+            if (m == 0xC2 && !(accept & PPY_JPEG_ACCEPT_PROGRESSIVE)) return fail(f, PPY_ERR_UNSUPPORTED, "progressive JPEG");
+            if (frame_segment(s, sl, P, M, f) != PPY_OK) return f.code;
+            P.progressive = m == 0xC2;
+        } else if (m != 0xDA) {
+            if (table_segment(m, s, sl, P, M, f) != PPY_OK) return f.code;
+        } else {
+            if (!M.sof) return fail(f, PPY_ERR_CORRUPT, "SOS before SOF");
+            if (scans == 0) {      // the frame, judged where parse() judges it
+                if (P.ncomp == 3) {
+                    if (rgb_file(P, M)) return fail(f, PPY_ERR_UNSUPPORTED, "RGB colour space (Adobe transform 0)");
+                    const int h = P.h[0], v = P.v[0];
+                    const bool chroma = P.h[1] == 1 && P.v[1] == 1 && P.h[2] == 1 && P.v[2] == 1;
+                    if (!(accept & PPY_JPEG_ACCEPT_SAMPLING)) {
+                        if (!chroma || !((h == 1 && v == 1) || (h == 2 && v == 1) || (h == 2 && v == 2)))
+                            return fail(f, PPY_ERR_UNSUPPORTED, "sampling factors other than 4:4:4, 4:2:2, 4:2:0");
+                    } else {
+                        if (h < 1 || h > 4 || v < 1 || v > 4) return fail(f, PPY_ERR_CORRUPT, "bad sampling factors");
+                        if (!chroma) return fail(f, PPY_ERR_UNSUPPORTED, "chroma sampling factors other than 1x1");
+                        if (h * v > 8) return fail(f, PPY_ERR_UNSUPPORTED, "sampling factors with more than 10 blocks in an MCU");
+                    }
+                } else {
+                    if (P.h[0] < 1 || P.h[0] > 4 || P.v[0] < 1 || P.v[0] > 4) return fail(f, PPY_ERR_CORRUPT, "bad sampling factors");
+                    P.h[0] = P.v[0] = 1;      // a one-component scan is never interleaved
+                }
+                frame_geometry(P);
+            }
+            Scan S;
+            if (scan_header(s, sl, accept, P, bits, latched, S, f) != PPY_OK) return f.code;
+            if (coef == nullptr) return PPY_OK;
+            if (++scans > 256) return fail(f, PPY_ERR_UNSUPPORTED, "more than 256 scans");
+            for (int k = 0; k < S.ns; ++k) {
+                const int c = S.c[k];
+                if (!latched[c]) memcpy(P.ql[c], P.q[P.tq[c]], sizeof(P.ql[c]));
+                latched[c] = true;
+                for (int j = S.ss; j <= S.se; ++j) bits[c][j] = (signed char)S.al;
+            }
+            if (run_scan(d, n, P, S, coef, i, f) != PPY_OK) return f.code;
+            while (i < n && !(d[i] == 0xFF && i + 1 < n && d[i + 1] != 0 && d[i + 1] != 0xFF)) ++i;      // to the marker
+        }
+    }
+    for (int c = 0; c < P.ncomp; ++c)
+        for (int j = 0; j < 64; ++j)
+            if (bits[c][j] != 0)
+                return P.progressive ? fail(f, PPY_ERR_UNSUPPORTED, "incomplete progressive scan script")
+                                     : fail(f, PPY_ERR_CORRUPT, "a component has no scan");
     return PPY_OK;
 }
 
@@ -373,7 +702,9 @@ struct JpegDev {
 };
 static_assert(sizeof(JpegDev) == 576 && offsetof(JpegDev, q) % 16 == 0, "JpegDev layout");
 
-enum { UP_NONE = 0, UP_H2V1_FANCY = 1, UP_H2V2_FANCY = 2, UP_H2V1_BOX = 3, UP_H2V2_BOX = 4 };
+// UP_H1V2_FANCY and UP_REPLICATE serve the further luma factors; UP_REPLICATE carries its two factors in the mode word
+// (UP_REPLICATE | fx << 8 | fy << 16), so JpegDev keeps its size.
+enum { UP_NONE = 0, UP_H2V1_FANCY = 1, UP_H2V2_FANCY = 2, UP_H2V1_BOX = 3, UP_H2V2_BOX = 4, UP_H1V2_FANCY = 5, UP_REPLICATE = 6 };
 
 #ifndef PPY_JPEG_HOST_ONLY
 typedef unsigned int u32;
@@ -475,6 +806,14 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const JpegDev *__restric
 // h2v1 / h2v2 upsamplers evaluated at one position.  Edges replicate at the DOWNSAMPLED size (dw x dh).
 __device__ __forceinline__ int jpeg_sample(const unsigned char *__restrict__ p, int pitch, int mode, int dw, int dh, int y, int x) {
     if (mode == UP_NONE) return p[(long long)y * pitch + x];
+    if (mode > UP_H2V2_BOX) {      // uniform over an image: jdsample.c's h1v2_fancy (vertical triangle filter) and int_upsample
+        if (mode == UP_H1V2_FANCY) {
+            const int j = y >> 1;
+            const int jn = (y & 1) ? (j + 1 < dh ? j + 1 : dh - 1) : (j > 0 ? j - 1 : 0);
+            return (3 * p[(long long)j * pitch + x] + p[(long long)jn * pitch + x] + ((y & 1) ? 2 : 1)) >> 2;
+        }
+        return p[(long long)(y / (mode >> 16)) * pitch + x / ((mode >> 8) & 255)];
+    }
     const int i = x >> 1;
     if (mode == UP_H2V1_BOX) return p[(long long)y * pitch + i];
     if (mode == UP_H2V2_BOX) return p[(long long)(y >> 1) * pitch + i];
@@ -537,7 +876,7 @@ bool desc_ok(const ppy_jpeg_desc_t &d) {
     if (d.components != 1 && d.components != 3) return false;
     if (d.orientation < 1 || d.orientation > 8) return false;
     const int hm = d.h_samp[0], vm = d.v_samp[0];
-    if (!((hm == 1 && vm == 1) || (d.components == 3 && hm == 2 && (vm == 1 || vm == 2)))) return false;
+    if (!((hm == 1 && vm == 1) || (d.components == 3 && hm >= 1 && hm <= 4 && vm >= 1 && vm <= 4 && hm * vm <= 8))) return false;
     const int mcux = (d.width + 8 * hm - 1) / (8 * hm), mcuy = (d.height + 8 * vm - 1) / (8 * vm);
     long long off = 0;
     for (int c = 0; c < d.components; ++c) {
@@ -570,7 +909,8 @@ static void fill_desc(const Parsed &P, ppy_jpeg_desc_t *h_desc) {      // everyt
         h_desc->blocks_w[c] = P.bw[c];
         h_desc->blocks_h[c] = P.bh[c];
         h_desc->coef_offset[c] = P.coef_off[c];
-        for (int k = 0; k < 64; ++k) h_desc->quant[c][stored_index(k)] = P.q[P.tq[c]][k];
+        const unsigned short *q = P.full ? P.ql[c] : P.q[P.tq[c]];
+        for (int k = 0; k < 64; ++k) h_desc->quant[c][stored_index(k)] = q[k];
     }
 }
 
@@ -588,36 +928,49 @@ static void fill_info(const Parsed &P, ppy_jpeg_info_t *info) {
         info->blocks_h[c] = P.bh[c];
     }
     info->coef_bytes = P.coef_elems * 2;
+    info->progressive = P.progressive;
 }
 
-extern "C" int ppy_jpeg_info(const unsigned char *h_data, size_t bytes, ppy_jpeg_info_t *h_info) {
-    if (h_data == nullptr || h_info == nullptr) return PPY_ERR_BAD_ARG;
+static const unsigned ACCEPT_ALL = PPY_JPEG_ACCEPT_PROGRESSIVE | PPY_JPEG_ACCEPT_MULTISCAN | PPY_JPEG_ACCEPT_SAMPLING;
+
+// Mask 0 is the single-scan path, call for call what it was before the mask existed; any other mask goes through the scan loop.
+extern "C" int ppy_jpeg_info_ex(const unsigned char *h_data, size_t bytes, unsigned accept, ppy_jpeg_info_t *h_info) {
+    if (h_data == nullptr || h_info == nullptr || (accept & ~ACCEPT_ALL) != 0) return PPY_ERR_BAD_ARG;
     memset(h_info, 0, sizeof(*h_info));
     Parsed P;
     Fail f = {PPY_OK, ""};
-    const int rc = parse(h_data, bytes, P, f);
+    const int rc = accept ? decode_full(h_data, bytes, accept, P, nullptr, f) : parse(h_data, bytes, P, f);
     if (rc == PPY_OK) fill_info(P, h_info);
     h_info->status = rc;
     memcpy(h_info->reason, f.reason, sizeof(f.reason));
     return rc;
 }
 
-extern "C" int ppy_jpeg_entropy_decode(const unsigned char *h_data, size_t bytes, int16_t *h_coef, size_t coef_bytes,
-                                       ppy_jpeg_desc_t *h_desc, char *h_reason) {
+extern "C" int ppy_jpeg_info(const unsigned char *h_data, size_t bytes, ppy_jpeg_info_t *h_info) {
+    return ppy_jpeg_info_ex(h_data, bytes, 0, h_info);
+}
+
+extern "C" int ppy_jpeg_entropy_decode_ex(const unsigned char *h_data, size_t bytes, unsigned accept, int16_t *h_coef, size_t coef_bytes,
+                                          ppy_jpeg_desc_t *h_desc, char *h_reason) {
     if (h_reason) h_reason[0] = 0;
-    if (h_data == nullptr || h_coef == nullptr || h_desc == nullptr) return PPY_ERR_BAD_ARG;
+    if (h_data == nullptr || h_coef == nullptr || h_desc == nullptr || (accept & ~ACCEPT_ALL) != 0) return PPY_ERR_BAD_ARG;
     Parsed P;
     Fail f = {PPY_OK, ""};
-    int rc = parse(h_data, bytes, P, f);
+    int rc = accept ? decode_full(h_data, bytes, accept, P, nullptr, f) : parse(h_data, bytes, P, f);
     if (rc == PPY_OK && (size_t)(P.coef_elems * 2) > coef_bytes) rc = fail(f, PPY_ERR_WORKSPACE, "coefficient buffer too small");
     if (rc == PPY_OK) {
-        memset(h_coef, 0, (size_t)P.coef_elems * 2);
-        rc = entropy_decode(h_data, bytes, P, h_coef, f);
+        memset(h_coef, 0, (size_t)P.coef_elems * 2);      // the blocks no scan visits stay zero
+        rc = accept ? decode_full(h_data, bytes, accept, P, h_coef, f) : entropy_decode(h_data, bytes, P, h_coef, f);
     }
     if (h_reason) memcpy(h_reason, f.reason, sizeof(f.reason));
     if (rc != PPY_OK) return rc;
     fill_desc(P, h_desc);
     return PPY_OK;
+}
+
+extern "C" int ppy_jpeg_entropy_decode(const unsigned char *h_data, size_t bytes, int16_t *h_coef, size_t coef_bytes,
+                                       ppy_jpeg_desc_t *h_desc, char *h_reason) {
+    return ppy_jpeg_entropy_decode_ex(h_data, bytes, 0, h_coef, coef_bytes, h_desc, h_reason);
 }
 
 // ------------------------------------------------------------------------------- host pre-pass of the device entropy mode
@@ -791,9 +1144,12 @@ extern "C" int ppy_jpeg_pack_table(int n, const ppy_jpeg_desc_t *h_descs, unsign
             const int hm = s.h_samp[0], vm = s.v_samp[0];
             d.dw[c] = (s.width * s.h_samp[c] + hm - 1) / hm;
             d.dh[c] = (s.height * s.v_samp[c] + vm - 1) / vm;
-            if (s.h_samp[c] == hm && s.v_samp[c] == vm) d.mode[c] = UP_NONE;
-            else if (s.v_samp[c] == vm) d.mode[c] = d.dw[c] > 2 ? UP_H2V1_FANCY : UP_H2V1_BOX;      // jdsample.c: fancy needs > 2 columns
-            else d.mode[c] = d.dw[c] > 2 ? UP_H2V2_FANCY : UP_H2V2_BOX;
+            const int fx = hm / s.h_samp[c], fy = vm / s.v_samp[c];      // jdsample.c jinit_upsampler, fancy upsampling on
+            if (fx == 1 && fy == 1) d.mode[c] = UP_NONE;
+            else if (fx == 2 && fy == 1) d.mode[c] = d.dw[c] > 2 ? UP_H2V1_FANCY : UP_H2V1_BOX;      // fancy needs > 2 columns
+            else if (fx == 2 && fy == 2) d.mode[c] = d.dw[c] > 2 ? UP_H2V2_FANCY : UP_H2V2_BOX;
+            else if (fx == 1 && fy == 2) d.mode[c] = UP_H1V2_FANCY;                                  // whatever the width
+            else d.mode[c] = UP_REPLICATE | fx << 8 | fy << 16;
             memcpy(d.q[c], s.quant[c], sizeof(d.q[c]));
         }
         tab[i] = d;

@@ -13,9 +13,11 @@ unstuffing, cutting at the restart markers: ppy_jpeg_scan_prepare), the compress
 and csrc/jpeg_entropy.hip fills the same coefficient buffer on the device, element for element.  Damage inside the entropy
 data is then found on the device and comes back as one status word per image.  The default stays 'host'.
 
-Baseline Huffman JPEG only (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0): anything else raises PPYoloHipError naming the reason, so a
-caller can hand that file to a decoder of its own.  A truncated or damaged file is an error too (libjpeg would fill the
-missing part with grey and warn).
+By default baseline Huffman JPEG only (grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan): anything else raises
+PPYoloHipError naming the reason, so a caller can hand that file to a decoder of its own.  JpegDecoder(accept='all') also takes
+progressive files, sequential files in several scans and the luma factors of 4:4:0 / 4:1:1 / 4:1:0 and their like (host entropy
+stage; the same two launches); arithmetic coding, 12-bit, CMYK / RGB and chroma factors other than 1x1 stay refused.  A
+truncated or damaged file is an error too (libjpeg would fill the missing part with grey and warn).
 
 JpegEncoder is the same codec run the other way: uint8 device images -> the bytes libjpeg-turbo writes with its defaults
 (cv2.imwrite, reference demo.py:50; Pillow's Image.save), byte for byte.  Both stages run on the device
@@ -49,6 +51,16 @@ def _refuse(i, rc, reason):
     return PPYoloHipError('item %d: %s: %s (code %d)' % (i, kind, reason.decode(errors='replace') or '?', rc))
 
 
+def _accept_mask(accept):
+    """'baseline' | 'all' | a subset of {'progressive', 'multiscan', 'sampling'} -> the PPY_JPEG_ACCEPT_* mask."""
+    if accept == 'baseline':
+        return 0
+    names = set(_lib.JPEG_ACCEPT) if accept == 'all' else {accept} if isinstance(accept, str) else set(accept)
+    if not names <= set(_lib.JPEG_ACCEPT):
+        raise PPYoloHipError("accept must be 'baseline', 'all' or a subset of %s, got %r" % (sorted(_lib.JPEG_ACCEPT), accept))
+    return sum(_lib.JPEG_ACCEPT[k] for k in names)
+
+
 class HostBatch(object):
     """Output of the entropy stage: descriptors + the pinned buffer holding [descriptor table | coefficients].  It OWNS one of
     the decoder's two staging buffers until it is passed to reconstruct() (which may be repeated until a later batch takes the
@@ -58,12 +70,20 @@ class HostBatch(object):
 
 
 class JpegDecoder(object):
-    def __init__(self, device='cuda', threads=None, apply_orientation=True, max_pixels=1 << 28, entropy='host', subseq_bytes=None):
+    def __init__(self, device='cuda', threads=None, apply_orientation=True, max_pixels=1 << 28, entropy='host', subseq_bytes=None,
+                 accept='baseline'):
         """entropy: 'host' (Huffman decoding on the thread pool) or 'device' (on the GPU; the pool runs the marker pass alone).
         subseq_bytes: device mode, bytes of compressed data per lane, a power of two in [8, 4096]; default 32 (8 and 16 decode faster in isolation: profiles/jpeg_bench_device_entropy.txt).
         threads: workers of the entropy stage, default min(16, images of the call); never more than 16, never derived from
         the machine's CPU count.  apply_orientation=False delivers the stored raster (cv2.IMREAD_IGNORE_ORIENTATION).
-        max_pixels: a header that claims more is refused before any buffer is sized from it (a few bytes can claim 65535 x 65535)."""
+        max_pixels: a header that claims more is refused before any buffer is sized from it (a few bytes can claim 65535 x 65535).
+        accept: 'baseline' (one interleaved scan, 4:4:4 / 4:2:2 / 4:2:0: everything else is refused by name), 'all', or any
+        subset of {'progressive', 'multiscan', 'sampling'}: progressive files, sequential files in several scans, and the luma
+        factors up to 4 x 4 with at most 8 luma blocks per MCU (4:4:0, 4:1:1, 4:1:0, ...).  Host entropy stage only."""
+        self.accept = _accept_mask(accept)
+        if entropy == 'device' and self.accept:
+            raise PPYoloHipError("the device entropy stage reads single-scan baseline files only: entropy='device' needs "
+                                 "accept='baseline', got %r" % (accept,))
         self.max_pixels = int(max_pixels)
         if entropy not in ('host', 'device'):
             raise PPYoloHipError("entropy must be 'host' or 'device', got %r" % (entropy,))
@@ -124,7 +144,7 @@ class JpegDecoder(object):
         Damage inside the entropy data still surfaces in decode()."""
         data = _bytes(item)
         info = _lib.JpegInfo()
-        rc = lib().ppy_jpeg_info(data, len(data), ctypes.byref(info))
+        rc = lib().ppy_jpeg_info_ex(data, len(data), self.accept, ctypes.byref(info))
         if rc == _lib.OK:
             return None
         return ('unsupported' if rc == -2 else 'corrupt'), info.reason.decode(errors='replace') or '?'
@@ -146,7 +166,7 @@ class JpegDecoder(object):
         total = table_bytes
         for i, d in enumerate(datas):
             info = _lib.JpegInfo()
-            rc = L.ppy_jpeg_info(d, len(d), ctypes.byref(info))
+            rc = L.ppy_jpeg_info_ex(d, len(d), self.accept, ctypes.byref(info))
             if rc != _lib.OK:
                 raise _refuse(i, rc, info.reason)
             if info.width * info.height > self.max_pixels:
@@ -162,7 +182,8 @@ class JpegDecoder(object):
 
         def one(i):
             reason = ctypes.create_string_buffer(64)
-            rc = L.ppy_jpeg_entropy_decode(datas[i], len(datas[i]), base + descs[i].coef_base, sizes[i][4], ctypes.byref(descs[i]), reason)
+            rc = L.ppy_jpeg_entropy_decode_ex(datas[i], len(datas[i]), self.accept, base + descs[i].coef_base, sizes[i][4], ctypes.byref(descs[i]),
+                                              reason)
             return rc, reason.value
 
         try:

@@ -16,6 +16,12 @@ Input: the COCO-sized files of tests/golden/g20_jpeg.npz replicated to a batch. 
                          (table + plan + compressed scan records); entropy_ms: the entropy launches of a batch replayed from a
                          graph, per subsequence size, beside reconstruct.ms; link_fixed: subsequences the cross-workgroup step
                          repaired; and in detect the legs files_device (status read back per batch) and files_device_nocheck.
+--progressive [--parent-lib PATH] runs, instead of all the above, the legs of the files JpegDecoder(accept='all') adds:
+  host_ms_per_image      the host stage at 1 and 16 threads on the progressive COCO-sized goldens (g22_jpeg_full.npz), on
+                         baseline files of the same pixels (default decoder, and accept='all'), and Pillow's whole decode;
+  reconstruct_ms         the two launches on a batch of 480x640 4:2:0 / 4:4:0 / 4:1:1 images, --rounds windows each, alternating;
+  baseline_reconstruct_ms  the two launches on the baseline batch, this library against the one at PATH (the parent commit's
+                         build), both loaded into this process, --rounds alternating windows.
 Every timed window lasts at least --window seconds (the repeat count is calibrated first); the detect legs alternate for
 --rounds rounds and report every round, so the spread is in the output.  One JSON line."""
 import argparse
@@ -78,6 +84,98 @@ def replay_ms(fn, window):
     return event_ms(g.replay, window)
 
 
+def progressive_legs(a):
+    """--progressive: the files JpegDecoder(accept='all') adds.  (a) host stage per image on the progressive COCO-sized goldens
+    beside baseline files of the same pixels and Pillow's whole decode; (b) the two reconstruct launches on 4:4:0, 4:1:1 and
+    4:2:0 images of one size; (c) the two launches on the baseline batch, this library against --parent-lib, alternating."""
+    import ctypes
+
+    import jpeg_full_fixtures as FF
+    import jpeg_full_synth as FS
+    import jpeg_synth as S
+    L = _lib.lib()
+    res = dict(bs=a.bs, device=torch.cuda.get_device_name(0))
+    prog = [FF.data(n) for n in FF.names() if '_coco_' in n]
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+        base, res['baseline_files'] = files(len(prog)), 'the originals (no Pillow to re-encode them)'
+    else:
+        def again(b):
+            bio = io.BytesIO()
+            Image.fromarray(np.asarray(Image.open(io.BytesIO(b)).convert('RGB'))).save(bio, 'JPEG', quality=75, subsampling=2)
+            return bio.getvalue()
+        base, res['baseline_files'] = [again(b) for b in files(len(prog))], 'Pillow, quality 75, 4:2:0, as the progressive ones'
+    res['file_bytes'] = dict(progressive=sum(map(len, prog)), baseline=sum(map(len, base)))
+    host = {}
+    for key, data, accept in (('progressive', prog, 'all'), ('baseline', base, 'baseline'), ('baseline_accept_all', base, 'all')):
+        host[key] = {}
+        for th in (1, 16):
+            jd = JpegDecoder(threads=th, accept=accept)
+            many = [data[i % len(data)] for i in range(4 * a.bs)]
+            host[key][str(th)] = wall_s(lambda: jd.release(jd.entropy_decode(many)), a.window) * 1e3 / len(many)
+    if Image is not None:
+        host['pillow_progressive'] = {}
+        for th in (1, 16):
+            pool = ThreadPoolExecutor(th)
+            many = [prog[i % len(prog)] for i in range(4 * a.bs)]
+            host['pillow_progressive'][str(th)] = wall_s(
+                lambda: list(pool.map(lambda b: np.asarray(Image.open(io.BytesIO(b)).convert('RGB')), many)), a.window) * 1e3 / len(many)
+            pool.shutdown()
+    res['host_ms_per_image'] = host
+
+    def launches(lib, hb, blob, ws):
+        coef_bytes = hb.total_bytes - hb.table_bytes
+
+        def run():
+            _lib.check(lib.ppy_jpeg_reconstruct_u8(hb.n, hb.descs, 1, blob.data_ptr(), blob.data_ptr() + hb.table_bytes, coef_bytes,
+                                                   ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream), 'ppy_jpeg_reconstruct_u8')
+        return run
+
+    # (b) one batch per sampling, all in one run
+    jd = JpegDecoder(accept='all')
+    rng = np.random.default_rng(7)
+    res['reconstruct_ms'] = {}
+    keep = []
+    for name, luma in (('420', (2, 2)), ('440', (1, 2)), ('411', (4, 1))):
+        one = S.encode(FS.synth(rng, 480, 640, luma))
+        hb = jd.entropy_decode([one] * a.bs)
+        outs = jd.reconstruct(hb)
+        blob = torch.empty(hb.total_bytes, dtype=torch.uint8, device='cuda')
+        blob.copy_(hb.stage[:hb.total_bytes])
+        torch.cuda.synchronize()
+        ws = torch.empty(L.ppy_jpeg_workspace_bytes(hb.n, hb.descs), dtype=torch.uint8, device='cuda')
+        keep.append((name, launches(L, hb, blob, ws), outs))
+    for _ in range(a.rounds):
+        for name, run, _ in keep:
+            res['reconstruct_ms'].setdefault(name, []).append(round(replay_ms(run, a.window), 5))
+
+    # (c) the baseline batch: this library against the parent's
+    if a.parent_lib:
+        parent = ctypes.CDLL(a.parent_lib)
+        for fn in ('ppy_jpeg_pack_table', 'ppy_jpeg_reconstruct_u8'):
+            getattr(parent, fn).restype, getattr(parent, fn).argtypes = _lib._PROTOS[fn]
+        jd0 = JpegDecoder()
+        hb = jd0.entropy_decode(files(a.bs))
+        outs = jd0.reconstruct(hb)              # packs this library's table into the staging buffer
+        torch.cuda.synchronize()
+        ws = torch.empty(L.ppy_jpeg_workspace_bytes(hb.n, hb.descs), dtype=torch.uint8, device='cuda')
+        legs = []
+        for key, lib in (('this', L), ('parent', parent)):
+            stage = hb.stage[:hb.total_bytes].clone()
+            _lib.check(lib.ppy_jpeg_pack_table(hb.n, hb.descs, (ctypes.c_void_p * hb.n)(*[t.data_ptr() for t in outs]),
+                                               (ctypes.c_longlong * hb.n)(*[3 * t.shape[1] for t in outs]), 1, stage.data_ptr(), hb.table_bytes),
+                       'ppy_jpeg_pack_table')
+            legs.append((key, launches(lib, hb, stage.cuda(), ws)))
+        ab = {'this': [], 'parent': []}
+        for _ in range(a.rounds):
+            for key, run in legs:
+                ab[key].append(round(replay_ms(run, a.window), 5))
+        res['baseline_reconstruct_ms'] = ab
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--bs', type=int, default=8)
@@ -85,8 +183,12 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--no-model', action='store_true')
     ap.add_argument('--entropy', choices=('host', 'device'), default='host')
+    ap.add_argument('--progressive', action='store_true', help='only the legs of the files accept= adds (progressive_legs)')
+    ap.add_argument('--parent-lib', default=None, help="--progressive: the parent commit's libppyolo_hip.so for the A/B leg")
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a ROCm device'
+    if a.progressive:
+        return progressive_legs(a)
     data = files(a.bs)
     L = _lib.lib()
     res = dict(bs=a.bs, device=torch.cuda.get_device_name(0), file_bytes=sum(len(d) for d in data))

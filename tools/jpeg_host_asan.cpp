@@ -1,10 +1,13 @@
-// Prefix and byte-flip sweep of the host JPEG stage (ppy_jpeg_info, ppy_jpeg_entropy_decode) for an AddressSanitizer build.
+// Prefix and byte-flip sweep of the host JPEG stage (ppy_jpeg_info_ex, ppy_jpeg_entropy_decode_ex) for an AddressSanitizer build.
 // Host code only: the device side of csrc/jpeg.hip is compiled out, nothing here touches a GPU.
 //
 //   clang++ -x c++ -DPPY_JPEG_HOST_ONLY -std=c++17 -g -O1 \
 //       -fsanitize=address,undefined -fno-sanitize-recover=all \
 //       pytorch-ppyolo_amd/ppyolo_hip/csrc/jpeg.hip tools/jpeg_host_asan.cpp -o /tmp/jpeg_host_asan
-//   /tmp/jpeg_host_asan FILE.jpg [FILE.jpg ...]
+//   /tmp/jpeg_host_asan [--accept MASK] FILE.jpg [FILE.jpg ...]
+//
+// MASK: the PPY_JPEG_ACCEPT_* bits, default 0 (the baseline subset); 7 takes progressive files, several scans and the further
+// luma sampling factors through the scan loop.
 //
 // Every input is copied into a heap block of exactly its size and the coefficient buffer has exactly coef_bytes, so a read or
 // write one byte outside either is reported.  Prints one line per file; exit status 0 = every call returned a status code.
@@ -15,17 +18,19 @@
 
 #include "../include/ppyolo_hip.h"
 
+static unsigned accept_mask = 0;
+
 static int run(const unsigned char *src, size_t n, long long *counts) {
     unsigned char *d = (unsigned char *)malloc(n ? n : 1);
-    memcpy(d, src, n);
+    if (n) memcpy(d, src, n);
     ppy_jpeg_info_t info;
-    int rc = ppy_jpeg_info(d, n, &info);
+    int rc = ppy_jpeg_info_ex(d, n, accept_mask, &info);
     if (rc == PPY_OK && info.coef_bytes <= (1ll << 26)) {
         int16_t *coef = (int16_t *)malloc((size_t)info.coef_bytes);
         ppy_jpeg_desc_t desc;
         memset(&desc, 0, sizeof(desc));
         char reason[64];
-        rc = ppy_jpeg_entropy_decode(d, n, coef, (size_t)info.coef_bytes, &desc, reason);
+        rc = ppy_jpeg_entropy_decode_ex(d, n, accept_mask, coef, (size_t)info.coef_bytes, &desc, reason);
         free(coef);
     }
     free(d);
@@ -36,7 +41,12 @@ static int run(const unsigned char *src, size_t n, long long *counts) {
 
 int main(int argc, char **argv) {
     int bad = 0;
-    for (int a = 1; a < argc; ++a) {
+    int first = 1;
+    if (argc > 2 && strcmp(argv[1], "--accept") == 0) {
+        accept_mask = (unsigned)strtoul(argv[2], nullptr, 0);
+        first = 3;
+    }
+    for (int a = first; a < argc; ++a) {
         FILE *f = fopen(argv[a], "rb");
         if (!f) return 2;
         std::vector<unsigned char> b;
