@@ -907,6 +907,30 @@ int ppy_draw_detections_u8(int n, const ppy_draw_image_t *h_images, const ppy_dr
                            const unsigned char *names, const int *name_len, const int *h_name_len, const unsigned char *font,
                            void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * GroupNorm and Mish of Conv2dUnit (reference model/custom_layers.py:37-43, :118-135; csrc/norm_act.hip).  Both work on the
+ * NHWC view (ptr, ld, N, H, W, C) every op takes: ld >= C, C and ld multiples of 4, pointers 16-byte aligned.
+ *
+ * ppy_group_norm_f32: torch.nn.GroupNorm(groups, C) of the RAW convolution output x -- statistics per (image, group) over
+ * H * W * C / groups elements, biased variance, eps inside the square root -- then `* gamma + beta`, [+ residual], act
+ * (PPY_ACT_NONE / _RELU / _LEAKY / _MISH): the residual is added after the affine and before the activation, the block-level
+ * relu(x + shortcut).  y may be a channel slice of a wider buffer; upsample2x != 0: y is the [N, 2H, 2W, C] destination and every
+ * pixel is stored to its 2 x 2 nearest-neighbour positions.  Three launches on `stream`, no host synchronisation, no
+ * floating-point atomics: sums of d = x - k and d * d per (image, pixel chunk, group) in double, k the group's own first element,
+ * combined in a fixed order, so the result is bit-identical from run to run and safe when a group's mean is large against its
+ * spread (no E[x^2] - E[x]^2 of the raw values; the mean stays a double up to `x - mean`).  ws: PPY_GN_WS_BYTES(N, groups) bytes, 8-byte aligned, owned by the call until the stream has run it.
+ * C % groups != 0 or a short workspace: PPY_ERR_BAD_ARG / PPY_ERR_WORKSPACE; C > 2048: PPY_ERR_UNSUPPORTED.
+ *
+ * ppy_mish_f32: x * tanh(softplus(x)) in place, softplus with torch's threshold (x > 20: x), evaluated as
+ * x * n / (n + 2) with n = e^x (e^x + 2), which has no cancellation. */
+#define PPY_ACT_MISH 3 /* norm_act.hip only: the convolution entry points reject it */
+#define PPY_GN_MAX_CHUNKS 128
+#define PPY_GN_WS_BYTES(N, groups) ((size_t)(N) * (size_t)(groups) * (PPY_GN_MAX_CHUNKS * 16 + 16))
+int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, const float *beta, int groups, float eps, int act,
+                       const float *residual, int res_ld, float *y, int y_ld, int upsample2x, int N, int H, int W, int C,
+                       void *ws, size_t ws_bytes, void *stream);
+int ppy_mish_f32(float *x, int x_ld, int N, int H, int W, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

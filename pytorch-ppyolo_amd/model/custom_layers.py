@@ -6,8 +6,9 @@ DropBlock :293-342, DCNv2 :486-523) so checkpoints and calling code are intercha
 but the classes here hold PARAMETERS ONLY.  Nothing is computed by torch: `emit()` records
 the layer into a kernel plan (ppyolo_hip/engine.py) and `forward()` of a single layer
 builds and runs a one-layer plan through the HIP kernels (used by the per-layer parity
-tests).  Eval mode only; GroupNorm / AffineChannel / Mish are not instantiated by either
-PP-YOLO config and raise NotImplementedError.
+tests).  Eval mode only.  GroupNorm / AffineChannel / Mish (reference :37-62, :118-135) are not instantiated by either
+PP-YOLO config but run on the inference path: AffineChannel folds into the convolution's epilogue like BatchNorm, GroupNorm and
+Mish are launches of their own behind it (csrc/norm_act.hip).  The training step stays BatchNorm only.
 """
 import torch
 
@@ -44,15 +45,23 @@ class DCNv2(torch.nn.Module):
             self.dcn_bias = torch.nn.Parameter(torch.zeros(filters))
 
 
+class AffineChannel(torch.nn.Module):
+    """Parameter holder of the per-channel scale and shift (reference :46-62): `weight`, `bias`, both [num_features]."""
+
+    def __init__(self, num_features):
+        super(AffineChannel, self).__init__()
+        self.weight = torch.nn.Parameter(torch.randn(num_features, ))
+        self.bias = torch.nn.Parameter(torch.randn(num_features, ))
+
+
 class Conv2dUnit(torch.nn.Module):
     def __init__(self, input_dim, filters, filter_size, stride=1, bias_attr=False, bn=0, gn=0, af=0, groups=32,
                  act=None, freeze_norm=False, is_test=False, norm_decay=0., lr=1., bias_lr=None, weight_init=None,
                  bias_init=None, use_dcn=False, name=''):
         super(Conv2dUnit, self).__init__()
-        if gn or af:
-            raise NotImplementedError('GroupNorm / AffineChannel are outside the PP-YOLO inference path')
-        if act not in (None, 'relu', 'leaky'):
-            raise NotImplementedError("Activation '%s' is not on the PP-YOLO inference path" % act)
+        if act not in (None, 'relu', 'leaky', 'mish'):
+            raise NotImplementedError("Activation '%s' is not implemented." % act)
+        self.groups = groups
         self.filters, self.filter_size, self.stride = filters, filter_size, stride
         self.padding = (filter_size - 1) // 2
         self.act_name = act
@@ -68,6 +77,8 @@ class Conv2dUnit(torch.nn.Module):
             self.conv = torch.nn.Conv2d(input_dim, filters, kernel_size=filter_size, stride=stride,
                                         padding=(filter_size - 1) // 2, bias=bias_attr)
         self.bn = torch.nn.BatchNorm2d(filters) if bn else None
+        self.gn = torch.nn.GroupNorm(num_groups=groups, num_channels=filters) if gn else None
+        self.af = AffineChannel(filters) if af else None
 
     # ---- training-loop surface (reference :141-243): which tensors train, and their optimizer groups ----
     def _own_params(self):
@@ -79,8 +90,9 @@ class Conv2dUnit(torch.nn.Module):
             ps = [(self.conv.weight, self.lr, True)]
             if self.conv.bias is not None:
                 ps.append((self.conv.bias, self.blr, False))
-        if self.bn is not None:
-            ps += [(self.bn.weight, self.lr, False), (self.bn.bias, self.lr, False)]
+        for norm in (self.bn, self.gn, self.af):          # (the reference's order, :203-241)
+            if norm is not None:
+                ps += [(norm.weight, self.lr, False), (norm.bias, self.lr, False)]
         return ps
 
     def freeze(self):
@@ -99,31 +111,66 @@ class Conv2dUnit(torch.nn.Module):
 
     # ---- plan emission -----------------------------------------------------------------------
     def folded(self, device):
+        """The per-channel (scale, shift) of the convolution's epilogue: eval BatchNorm and / or AffineChannel over the conv bias
+        (y = conv(x) * weight + bias, reference :52-62 -> (af.weight, af.bias + conv_bias * af.weight)); a GroupNorm unit keeps
+        (1, conv bias) there -- its norm is the 'gn' op behind the convolution."""
         bias = self.conv.dcn_bias if self.use_dcn else self.conv.bias
-        return _engine.fold_bn(self.bn, bias, self.filters, device)
+        scale, shift = _engine.fold_bn(self.bn, bias, self.filters, device)
+        if self.af is not None:
+            w = self.af.weight.detach().float()
+            scale, shift = (scale * w).contiguous(), (self.af.bias.detach().float() + shift * w).contiguous()
+        return scale, shift
 
     def emit(self, b, x, res=None, out=None, ups=False, coord=False, post_act=None):
         """Record conv -> BN -> [+res] -> act into builder `b`; returns the output activation.
         `post_act` is the block-level activation applied after the residual add (the unit's own
-        act is None there: reference model/resnet_vd.py:27, :55-56)."""
+        act is None there: reference model/resnet_vd.py:27, :55-56).
+        A GroupNorm unit records the raw convolution (scale 1, shift = conv bias, no activation, no residual) into a scratch
+        activation and a 'gn' op behind it that carries res / post_act / out / ups; a Mish unit without GroupNorm records the
+        convolution with act=None and a 'mish' op on its output."""
         act = self.act_name
         if res is not None:
             assert act is None
             act = post_act
+        if self.gn is not None:
+            if self.bn is not None or self.af is not None:
+                raise NotImplementedError('%s: GroupNorm combined with another norm' % (self.name or 'Conv2dUnit'))
+            return self._emit_gn(b, x, res, out, ups, coord, act)
+        mish, conv_act = act == 'mish', None if act == 'mish' else act
         skel = getattr(b, 'skeleton', False)      # shape-only plan: the executor takes the folded weights from their owner
         scale, shift = (None, None) if skel else self.folded(b.device)
         if x is None:
             # first backbone conv: reads the plan's NCHW input directly (3 -> K, 3x3, stride 2)
             assert (self.conv.in_channels, self.filter_size, self.stride) == (3, 3, 2) and not self.use_dcn
-            return b.stem(self.conv.weight, scale, shift, self.act_name)
-        if self.use_dcn:
+            y = b.stem(self.conv.weight, scale, shift, conv_act)
+        elif self.use_dcn:
             assert res is None and not ups and not coord
             co = self.conv.conv_offset
             one = None if skel else torch.ones(27, dtype=torch.float32, device=b.device)
             om = b.conv(x, co.weight, one, None if skel else co.bias.detach().float().clone(), stride=self.stride, act=None)
-            return b.dcn(x, om, self.conv.dcn_weight, scale, shift, self.stride, self.act_name, out=out)
-        return b.conv(x, self.conv.weight, scale, shift, stride=self.stride, act=act, res=res, out=out,
-                      ups=ups, coord=coord)
+            y = b.dcn(x, om, self.conv.dcn_weight, scale, shift, self.stride, conv_act, out=out)
+        else:
+            y = b.conv(x, self.conv.weight, scale, shift, stride=self.stride, act=conv_act, res=res, out=out,
+                       ups=ups, coord=coord)
+        return b.mish(y) if mish else y
+
+    def _emit_gn(self, b, x, res, out, ups, coord, act):
+        skel = getattr(b, 'skeleton', False)
+        one, bias = (None, None) if skel else self.folded(b.device)          # (1, conv bias or 0)
+        if x is None:
+            assert (self.conv.in_channels, self.filter_size, self.stride) == (3, 3, 2) and not self.use_dcn
+            raw = b.stem(self.conv.weight, one, bias, None)
+        elif self.use_dcn:
+            assert res is None and not ups and not coord
+            co = self.conv.conv_offset
+            o27 = None if skel else torch.ones(27, dtype=torch.float32, device=b.device)
+            om = b.conv(x, co.weight, o27, None if skel else co.bias.detach().float().clone(), stride=self.stride, act=None)
+            raw = b.dcn(x, om, self.conv.dcn_weight, one, bias, self.stride, None)
+        else:
+            raw = b.conv(x, self.conv.weight, one, bias, stride=self.stride, act=None, coord=coord)      # (CoordConv's bias: the conv's)
+        gamma = None if skel else self.gn.weight.detach().float().contiguous()
+        beta = None if skel else self.gn.bias.detach().float().contiguous()
+        return b.group_norm(raw, gamma, beta, self.gn.num_groups, self.gn.eps, act, res=res, out=out, ups=ups)
 
     def forward(self, x):
         """Single-layer HIP execution on an NCHW tensor (parity tests / drop-in use of one
@@ -142,12 +189,12 @@ class CoordConv(torch.nn.Module):
 
 
 class SPP(torch.nn.Module):
-    """Marker for SPP (reference :275-290, 'asc' order [x, pool5, pool9, pool13])."""
+    """Marker for SPP (reference :275-290): 'asc' order [x, pool5, pool9, pool13], 'desc' [pool13, pool9, pool5, x] -- the same
+    launch with the channel offsets of the concat reversed (engine.Builder.spp)."""
 
     def __init__(self, seq='asc'):
         super(SPP, self).__init__()
-        if seq != 'asc':
-            raise NotImplementedError('only the asc order used by PP-YOLO')
+        assert seq in ['desc', 'asc']
         self.seq = seq
 
 

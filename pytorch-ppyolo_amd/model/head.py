@@ -72,12 +72,12 @@ class DetectionBlock(torch.nn.Module):
                                               'demo.py:93); DropBlock in training mode runs in the training step -- '
                                               'model(x, None, False, ...) / ppyolo_hip.train.TrainStep')
             elif isinstance(ly, SPP):
-                x = b.spp(x)            # x is slot 0 of the 4C buffer (arranged below)
+                x = b.spp(x, desc=ly.seq == 'desc')            # x is slot 0 (asc) / 3 (desc) of the 4C buffer (arranged below)
             else:
                 out = None
                 if k + 1 < len(seq) and isinstance(seq[k + 1], SPP):
                     wide = b.new_act(x.N, x.H, x.W, 4 * ly.filters)
-                    out = b.slice(wide, 0, ly.filters)
+                    out = b.slice(wide, 3 * ly.filters if seq[k + 1].seq == 'desc' else 0, ly.filters)
                 x = ly.emit(b, x, out=out, coord=coord)
                 coord = False
         return x

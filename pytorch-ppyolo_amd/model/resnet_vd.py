@@ -64,10 +64,14 @@ class ConvBlock(_Units, torch.nn.Module):
             f = b.fold_shortcut = os.environ.get('PPYOLO_HIP_FOLD_SHORTCUT', '1') == '1'
         return f
 
+    def _folds(self, b):
+        """The fold needs conv3 and conv4 to END in a per-channel affine (BatchNorm, AffineChannel); GroupNorm is no such thing."""
+        return self._fold(b) and self.conv3.gn is None and self.conv4.gn is None and self.conv2.gn is None
+
     def wide_input(self, b, N, H, W):
         """Stage 2 (no pooling in front of the projection): the block's INPUT is the shortcut operand, so its producer writes it
         straight into the wide buffer -> the slice to hand to that producer (None when the fold is off)."""
-        if not (self._fold(b) and self.is_first):
+        if not (self._folds(b) and self.is_first):
             return None
         f2, cs = self.conv2.filters, self.conv4.conv.in_channels
         wide = b.new_buf(N, H, W, f2 + cs)
@@ -78,7 +82,7 @@ class ConvBlock(_Units, torch.nn.Module):
     def emit(self, b, x, out=None):
         # (a stage-2 block whose input was NOT placed into a wide buffer by its producer -- stand-alone emission, another stem -- takes
         # the unfolded path: the fold needs the producer's cooperation there, wide_input())
-        if self._fold(b) and not (self.is_first and not (id(self) in b.wide_of_block and x.buf == b.wide_of_block[id(self)])):
+        if self._folds(b) and not (self.is_first and not (id(self) in b.wide_of_block and x.buf == b.wide_of_block[id(self)])):
             return self._emit_folded(b, x, out)
         b.wide_of_block.pop(id(self), None)
         with b.side():              # projection shortcut: independent of conv1 -> conv2

@@ -16,6 +16,8 @@ LIB_PATH = os.environ.get('PPYOLO_HIP_LIB') or os.path.join(_HERE, 'lib', 'libpp
 OK = 0
 ERR_UNSUPPORTED = -2      # PPY_ERR_UNSUPPORTED (include/ppyolo_hip.h)
 ACT = {None: 0, 'relu': 1, 'leaky': 2}
+NORM_ACT = dict(ACT, mish=3)      # PPY_ACT_MISH: ppy_group_norm_f32 only (the convolution entry points reject it)
+GN_MAX_CHUNKS = 128               # PPY_GN_MAX_CHUNKS
 
 
 class PPYoloHipError(RuntimeError):
@@ -234,6 +236,9 @@ _PROTOS = {
     'ppy_jpeg_enc_scan_host': (c_int, [ctypes.POINTER(JpegEncDesc), c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_void_p]),
     'ppy_draw_detections_u8': (c_int, [c_int, ctypes.POINTER(DrawImage), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int,
                                        c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p, c_void_p]),
+    'ppy_group_norm_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_int]
+                           + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
+    'ppy_mish_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 

@@ -74,7 +74,7 @@ def save(ex, path, fp):
     for name in ('setup_ops', 'ops'):
         ents = []
         for op in getattr(ex.plan, name):
-            if op.get('w') is None:
+            if op.get('w') is None and op.get('op') != 'gn':      # (a 'gn' op carries gamma / beta as its scale / shift)
                 ents.append(None)
                 continue
             rec = {}

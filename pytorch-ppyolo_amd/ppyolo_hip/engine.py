@@ -230,12 +230,37 @@ class Builder(object):
         self._emit(dict(op='avgpool', x=x, y=y))
         return y
 
-    def spp(self, x_slot0):
-        """x_slot0: slice [0,C) of a [N,H,W,4C] buffer; fills slices 1..3 with pool 5/9/13."""
+    def spp(self, x_slot0, desc=False):
+        """x_slot0: slice [0,C) of a [N,H,W,4C] buffer; fills slices 1..3 with pool 5/9/13.  desc (SPP(seq='desc'), reference
+        model/custom_layers.py:286-287: [pool13, pool9, pool5, x]): the input sits in the LAST slice and the pools in front of it --
+        the same launch, other channel offsets."""
         C = x_slot0.C
+        if desc:
+            ys = [self.slice(x_slot0, -C * i, C) for i in (1, 2, 3)]
+            self._emit(dict(op='spp', x=x_slot0, y5=ys[0], y9=ys[1], y13=ys[2]))
+            return A(x_slot0.buf, x_slot0.coff - 3 * C, 4 * C, x_slot0.N, x_slot0.H, x_slot0.W)
         ys = [self.slice(x_slot0, C * i, C) for i in (1, 2, 3)]
         self._emit(dict(op='spp', x=x_slot0, y5=ys[0], y9=ys[1], y13=ys[2]))
         return A(x_slot0.buf, x_slot0.coff, 4 * C, x_slot0.N, x_slot0.H, x_slot0.W)
+
+    def group_norm(self, x, gamma, beta, groups, eps, act, res=None, out=None, ups=False):
+        """torch.nn.GroupNorm(groups, C) of the raw convolution output x, [+ res], act ('relu' / 'leaky' / 'mish' / None) -- three
+        launches of ppy_group_norm_f32.  gamma / beta travel as the op's 'scale' / 'shift' (what a weight owner hands on).  out: a
+        channel slice of a concat buffer; ups: the 2 x 2 nearest-upsampled destination the route convolutions write."""
+        if x.C % groups:
+            raise ValueError('num_channels must be divisible by num_groups')
+        up = 2 if ups else 1
+        y = self.new_act(x.N, up * x.H, up * x.W, x.C) if out is None else out
+        assert (y.N, y.H, y.W, y.C) == (x.N, up * x.H, up * x.W, x.C)
+        if res is not None:
+            assert (res.C, res.H, res.W) == (x.C, x.H, x.W)
+        self._emit(dict(op='gn', x=x, y=y, scale=gamma, shift=beta, groups=int(groups), eps=float(eps), act=act, res=res, ups=bool(ups)))
+        return y
+
+    def mish(self, x):
+        """x * tanh(softplus(x)) in place (ppy_mish_f32): behind the convolution of a bn / af + mish unit."""
+        self._emit(dict(op='mish', x=x, y=x))
+        return x
 
     def dcn(self, x, om, weight, scale, shift, stride, act, out=None):
         Kout = weight.shape[0]
@@ -501,6 +526,11 @@ class HipExecutor(object):
             self.ws = torch.empty(((need + 3) // 4,), dtype=torch.float32, device=self.device)
         if self.ws_side is None or self.ws_side.numel() * 4 < need_side:      # concurrent branch: own scratch
             self.ws_side = torch.empty(((need_side + 3) // 4,), dtype=torch.float32, device=self.device)
+        # GroupNorm's partial sums and statistics: launches of one stream follow each other, so one block per stream serves them all
+        gn = [op['groups'] for op in self.plan.ops if op['op'] == 'gn']
+        if gn and getattr(self, 'gn_ws', None) is None:
+            self.gn_ws = K.group_norm_workspace(self.plan.N, max(gn), self.device)
+            self.gn_ws_side = K.group_norm_workspace(self.plan.N, max(gn), self.device)
 
     def _run_op(self, op, ws=None):
         t = op['op']
@@ -550,6 +580,12 @@ class HipExecutor(object):
             K.dcnv2(self.view(op['x']), op['w'], op['scale'], op['shift'], self.view(op['om']), self.view(op['y']),
                     op['stride'], op['pad'], op['act'], ws, op['cfg'], op['splitk'], op.get('w3'), op.get('wf16'),
                     self._amax(op.get('amax_in_id')), self._amax(op.get('amax_out_id')))
+        elif t == 'gn':
+            K.group_norm(self.view(op['x']), op['scale'], op['shift'], op['groups'], op['eps'], self.view(op['y']), op['act'],
+                         None if op['res'] is None else self.view(op['res']), op['ups'],
+                         self.gn_ws_side if ws is self.ws_side else self.gn_ws)
+        elif t == 'mish':
+            K.mish(self.view(op['x']))
         else:
             raise PPYoloHipError('unknown plan op %r' % t)
 

@@ -591,6 +591,34 @@ def avgpool2x2(x, y):
     check(lib().ppy_avgpool2x2_f32(x.ptr, x.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C, _stream()), 'ppy_avgpool2x2_f32')
 
 
+def group_norm_workspace(N, groups, device):
+    """PPY_GN_WS_BYTES(N, groups): the partial sums and statistics of one ppy_group_norm_f32 call in flight."""
+    return torch.empty((N * groups * (_lib.GN_MAX_CHUNKS * 16 + 16) // 4,), dtype=torch.float32, device=device)
+
+
+def group_norm(x, gamma, beta, groups, eps, y, act=None, residual=None, upsample2x=False, ws=None):
+    """x, y, residual: View.  torch.nn.GroupNorm(groups, C)(x) [+ residual] -> act ('relu' / 'leaky' / 'mish' / None) into y; with
+    upsample2x y is the [N, 2H, 2W, C] nearest-neighbour destination.  See ppy_group_norm_f32.  Returns the workspace used."""
+    _dev(x.t, gamma, beta, y.t, None if residual is None else residual.t)
+    up = 2 if upsample2x else 1
+    assert y.C == x.C and (y.N, y.H, y.W) == (x.N, up * x.H, up * x.W) and gamma.numel() == x.C and beta.numel() == x.C
+    assert gamma.is_contiguous() and beta.is_contiguous() and gamma.dtype == torch.float32 and beta.dtype == torch.float32
+    assert residual is None or (residual.N, residual.H, residual.W, residual.C) == (x.N, x.H, x.W, x.C)
+    if ws is None:
+        ws = group_norm_workspace(x.N, groups, x.t.device)
+    check(lib().ppy_group_norm_f32(x.ptr, x.ld, gamma.data_ptr(), beta.data_ptr(), int(groups), float(eps), _lib.NORM_ACT[act],
+                                   None if residual is None else residual.ptr, 0 if residual is None else residual.ld, y.ptr, y.ld,
+                                   int(bool(upsample2x)), x.N, x.H, x.W, x.C, ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+          'ppy_group_norm_f32')
+    return ws
+
+
+def mish(x):
+    """x * tanh(softplus(x)) in place on a View (ppy_mish_f32)."""
+    _dev(x.t)
+    check(lib().ppy_mish_f32(x.ptr, x.ld, x.N, x.H, x.W, x.C, _stream()), 'ppy_mish_f32')
+
+
 def spp(x, y5, y9, y13):
     _dev(x.t, y5.t)
     assert y5.ld == y9.ld == y13.ld

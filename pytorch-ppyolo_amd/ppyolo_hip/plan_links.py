@@ -64,6 +64,10 @@ def op_io(op):
         return [op['x'].buf], [op['y5'].buf]
     if t == 'dcn':
         return [op['x'].buf, op['om'].buf], [op['y'].buf]
+    if t == 'gn':
+        return [op['x'].buf] + ([op['res'].buf] if op['res'] is not None else []), [op['y'].buf]
+    if t == 'mish':          # in place: a second writer of its buffer, which keeps every link rule off the convolution in front of it
+        return [op['x'].buf], [op['x'].buf]
     raise PPYoloHipError('unknown plan op %r' % t)
 
 
@@ -88,11 +92,25 @@ def assign_amax(ops):
     [conv2 output | pooled block input] -- the buffer gets a block of its OWN for what convolutions write and keeps the inherited
     one as a second, read-only block ('amax_in2_id' of its readers): the block input's other readers (the head's C3 / C4
     convolutions) no longer see conv2's maximum (round-5 advisor).  Only ppy_conv2d_bn_act_split_f32 takes the
-    second block: link_pools, link_maxpools and b2b_pairs leave a convolution that carries 'amax_in2_id' a launch of its own."""
-    amax_of, aux_of, inherited, nblocks = {}, {}, set(), 0
+    second block: link_pools, link_maxpools and b2b_pairs leave a convolution that carries 'amax_in2_id' a launch of its own.
+    GroupNorm and Mish: ppy_group_norm_f32 tracks nothing, so the buffer a 'gn' op writes into has NO block, whoever else writes into
+    it (a concat buffer shared with convolutions included) -- its readers get amax_in_id None, has_f16 is false for them and they run
+    on the non-f16x2 tiles.  |mish(x)| <= |x|, so a 'mish' op (in place) keeps its buffer's block, as pooling does: the maximum the
+    convolution in front of it tracked still bounds what the readers see."""
+    amax_of, aux_of, inherited, untracked, nblocks = {}, {}, set(), set(), 0
     for op in ops:
         t = op['op']
-        if t in ('conv', 'dcn'):
+        if t == 'gn':
+            b = op['y'].buf
+            untracked.add(b)
+            inherited.discard(b)
+            amax_of.pop(b, None)
+            aux_of.pop(b, None)
+        elif t in ('conv', 'dcn') and op['y'].buf in untracked:
+            op['amax_out_id'] = None
+            op['amax_in_id'] = amax_of.get(op['x'].buf)
+            op['amax_in2_id'] = aux_of.get(op['x'].buf)
+        elif t in ('conv', 'dcn'):
             b = op['y'].buf
             if b in inherited:
                 inherited.discard(b)
@@ -105,7 +123,7 @@ def assign_amax(ops):
             op['amax_in2_id'] = aux_of.get(op['x'].buf)
         elif t in ('maxpool', 'avgpool'):
             src = amax_of.get(op['x'].buf)
-            if src is not None:
+            if src is not None and op['y'].buf not in untracked:
                 yb = op['y'].buf
                 if yb in amax_of and yb not in inherited:      # a convolution wrote into this buffer first: second block
                     aux_of[yb] = src

@@ -66,6 +66,16 @@ def synth_state_dict(shapes, seed=0, num_classes=80, iou_aware=None):
                 out[name] = rand(shape, 0.6, 1.4)
             else:
                 raise KeyError(name)
+        elif '.gn.' in name or '.af.' in name:
+            # GroupNorm / AffineChannel scales and offsets: BatchNorm's rules (the branches above draw nothing for them, so the
+            # tensors of a bn model are what they were)
+            tail = name.startswith('backbone.stage') and any(t.replace('.bn.', n) in name for t in tails for n in ('.gn.', '.af.'))
+            if leaf == 'weight':
+                out[name] = rand(shape, 0.25, 0.55) if tail else rand(shape, 0.7, 1.3)
+            elif leaf == 'bias':
+                out[name] = randn(shape, 0.1)
+            else:
+                raise KeyError(name)
         elif 'conv_offset.weight' in name:
             out[name] = randn(shape, 2.0 / math.sqrt(_fan_in(shape)))
         elif 'conv_offset.bias' in name:

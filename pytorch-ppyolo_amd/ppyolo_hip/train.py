@@ -124,6 +124,20 @@ class ModelSettings(object):
         return bool(dropping) and not all(m.is_test for m in dropping)
 
 
+def check_bn_only(model):
+    """The training kernels implement BatchNorm and relu / leaky only: a unit with GroupNorm, AffineChannel or Mish (inference path:
+    csrc/norm_act.hip) is refused here, by name, instead of failing later on a missing `.bn.` key."""
+    for name, m in model.named_modules():
+        if type(m).__name__ != 'Conv2dUnit':
+            continue
+        odd = [what for what, there in (('GroupNorm', getattr(m, 'gn', None) is not None),
+                                        ('AffineChannel', getattr(m, 'af', None) is not None),
+                                        ('Mish', getattr(m, 'act_name', None) == 'mish')) if there]
+        if odd:
+            raise PPYoloHipError('%s (%s) holds %s: the training step implements BatchNorm with relu / leaky only -- such models run on '
+                                 'the inference path' % (name, getattr(m, 'name', '') or 'Conv2dUnit', ' + '.join(odd)))
+
+
 class TrainStep(object):
     def __init__(self, model, cfg=None, world_size=1, external_optimizer=False, seed_rank=None):
         """cfg: a configuration object (config/ppyolo_2x.py), or None = read the settings from the model's own objects.
@@ -132,6 +146,7 @@ class TrainStep(object):
         dev = next(model.parameters()).device
         if dev.type != 'cuda':
             raise PPYoloHipError('the training step needs the model on a ROCm device (got %s); there is no CPU path' % dev)
+        check_bn_only(model)
         cfg = ModelSettings(model) if cfg is None else cfg
         self.freeze_at = int(cfg.backbone.get('freeze_at', 5))
         if not 0 <= self.freeze_at <= 5:

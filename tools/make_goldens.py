@@ -1045,8 +1045,190 @@ def g19_augment():
     save('g19_augment', **arrs)
 
 
+def _g23_run(m, *xs):
+    """(float32 output, float64 output of a .double() copy) of a reference module."""
+    import copy
+    m.eval()
+    with torch.no_grad():
+        y32 = m(*xs)
+        y64 = copy.deepcopy(m).double()(*[x.double() for x in xs])
+    return y32, y64
+
+
+def _g23_fill(m, g):
+    """Random parameters for every Conv2dUnit below `m` (the reference leaves GroupNorm at identity and DCN offsets at zero)."""
+    with torch.no_grad():
+        for u in [u for u in m.modules() if isinstance(u, Conv2dUnit)]:
+            if isinstance(u.conv, DCNv2):
+                ci = u.conv.dcn_weight.shape[1]
+                u.conv.conv_offset.weight.copy_(torch.randn(u.conv.conv_offset.weight.shape, generator=g) * (2.0 / (ci * 9) ** 0.5))
+                u.conv.conv_offset.bias.copy_(torch.randn(27, generator=g) * 0.5)
+                u.conv.dcn_weight.copy_(torch.randn(u.conv.dcn_weight.shape, generator=g) * (2.0 / (ci * 9)) ** 0.5)
+            else:
+                w = u.conv.weight
+                w.copy_(torch.randn(w.shape, generator=g) * (2.0 / (w.shape[1] * w.shape[2] * w.shape[3])) ** 0.5)
+                if u.conv.bias is not None:
+                    u.conv.bias.copy_(torch.randn(w.shape[0], generator=g) * 0.5)
+            for norm in (u.bn, u.gn, u.af):
+                if norm is not None:
+                    norm.weight.copy_(torch.rand(norm.weight.shape, generator=g) + 0.5)
+                    norm.bias.copy_(torch.randn(norm.bias.shape, generator=g) * 0.2)
+            if u.bn is not None:
+                u.bn.running_mean.copy_(torch.randn(u.bn.running_mean.shape, generator=g) * 0.2)
+                u.bn.running_var.copy_(torch.rand(u.bn.running_var.shape, generator=g) + 0.5)
+
+
+def g23_norm_act():
+    """GroupNorm / AffineChannel / Mish of Conv2dUnit (reference model/custom_layers.py:37-62, :118-135, :243-253): unit, block and
+    model cases, each with its inputs, its state_dict, the reference's float32 output and the output of the same modules in
+    .double(), kept as `d64`, the float32 difference to the float32 output (half the bytes of the float64 tensor, exact to 6e-8 of
+    that difference: y64 = y32 + d64).  Four files, each below the size limit of a committed file: g23_norm_act.npz (units),
+    g23_norm_act_blocks.npz, g23_norm_act_r18vd_64.npz and g23_norm_act_r50vd_96.npz (models)."""
+    from model.resnet_vd import IdentityBlock, ConvBlock
+    g = gen(2323)
+    out = {}
+    NORM = {'bn': dict(bn=1), 'gn': dict(gn=1), 'af': dict(af=1)}
+    # norm, act, cin, cout, k, stride, bias, groups, N, H, W, special
+    units = [
+        ('gn', None, 32, 32, 3, 1, False, 32, 2, 13, 11, ''),
+        ('gn', 'relu', 32, 64, 1, 1, True, 32, 2, 13, 11, ''),
+        ('gn', 'leaky', 32, 256, 1, 2, False, 32, 2, 13, 11, ''),
+        ('gn', 'mish', 32, 32, 3, 2, True, 4, 2, 13, 11, ''),
+        ('gn', 'leaky', 32, 32, 1, 1, True, 32, 2, 1, 1, 'one'),          # H = W = 1, C / groups = 1: variance 0, output beta
+        ('gn', 'relu', 32, 64, 1, 1, True, 32, 2, 13, 11, 'const'),        # group 0's convolution output is constant
+        ('gn', 'leaky', 32, 64, 1, 1, True, 32, 2, 13, 11, 'mean'),        # group 1: mean ~1e3, spread ~1e-2
+        ('af', 'leaky', 32, 32, 3, 1, True, 32, 2, 13, 11, ''),
+        ('af', 'mish', 32, 32, 1, 2, False, 32, 2, 13, 11, ''),
+        ('bn', 'mish', 32, 32, 3, 2, False, 32, 2, 13, 11, ''),
+        ('af', 'mish', 32, 32, 1, 1, False, 32, 1, 3, 4, 'mish'),          # identity convolution over the Mish probe values
+    ]
+    probe = torch.tensor([-100., -20., -1e-3, 0., 1e-3, 19.99, 20., 20.01, 100., -5., 5., 1.])
+    surf = {}
+    for i, (norm, act, ci, co, k, s, bias, groups, N, H, W, special) in enumerate(units):
+        m = Conv2dUnit(ci, co, k, stride=s, bias_attr=bias, groups=groups, act=act, lr=2.0, bias_lr=3.0, **NORM[norm])
+        _g23_fill(m, g)
+        if (H, W) == (13, 11):                                # one input serves every case of this shape
+            if 'ux' not in out:
+                out['ux'] = torch.randn(N, ci, H, W, generator=g)
+                out['ux'][-1] = out['ux'][-1] * 3.0 + 0.5        # other statistics per image
+            x = out['ux']
+        else:
+            x = torch.randn(N, ci, H, W, generator=g)
+            x[-1] = x[-1] * 3.0 + 0.5
+        with torch.no_grad():
+            if special == 'const':
+                m.conv.weight[0:2] = 0.0
+                m.conv.bias[0:2] = 0.7
+            if special == 'mean':
+                m.conv.weight[2:4] *= 1e-2
+                m.conv.bias[2:4] = 1000.0
+            if special == 'mish':
+                m.conv.weight.copy_(torch.eye(ci).view(ci, ci, 1, 1))
+                m.af.weight.fill_(1.0)
+                m.af.bias.fill_(0.0)
+                x = torch.randn(N, ci, H, W, generator=g) * 4.0
+                x[0, :, :, :] = probe.view(1, H, W) + 0.0 * x[0]
+                x[0, 1::2] = x[0, 1::2].flip(-1)
+        y32, y64 = _g23_run(m, x)
+        p = 'u%d_' % i
+        out[p + 'meta'] = np.array(repr(dict(norm=norm, act=act, cin=ci, cout=co, k=k, stride=s, bias=bias, groups=groups, special=special)))
+        if x is not out.get('ux'):
+            out[p + 'x'] = x
+        out[p + 'y32'], out[p + 'd64'] = y32, (y64 - y32.double()).float()
+        for key, v in m.state_dict().items():
+            out[p + 'sd.' + key] = v
+        pg = []
+        m.add_param_group(pg, 0.01, 5e-4)
+        names = {id(v): key for key, v in m.named_parameters()}
+        surf[p] = dict(keys=[(key, tuple(v.shape)) for key, v in m.state_dict().items()],
+                       groups=[(names[id(gr['params'][0])], gr['lr'], gr['base_lr'], gr['weight_decay']) for gr in pg])
+    out['nunits'] = np.array(len(units))
+    out['surface'] = np.array(repr(surf))
+    save('g23_norm_act', **out)
+    out = {}
+
+    def run(p, m, *xs):
+        y32, y64 = _g23_run(m, *xs)
+        out[p + 'y32'], out[p + 'd64'] = y32, (y64 - y32.double()).float()
+
+    def block_sd(p, m):
+        for key, v in m.state_dict().items():
+            out[p + 'sd.' + key] = v
+
+    # IdentityBlock / ConvBlock of Resnet50Vd with gn: the residual is added after the norm
+    m = IdentityBlock(128, [32, 32, 128], 0, 1, 0, False, 0., 1.)
+    _g23_fill(m, g)
+    x = torch.randn(2, 128, 9, 7, generator=g)
+    out['b0_x'] = x
+    run('b0_', m, x)
+    block_sd('b0_', m)
+    m = ConvBlock(64, [32, 32, 128], 0, 1, 0, False, 0., 1., stride=2)
+    _g23_fill(m, g)
+    x = torch.randn(2, 64, 10, 8, generator=g)
+    out['b1_x'] = x
+    run('b1_', m, x)
+    block_sd('b1_', m)
+
+    # a head route: gn conv -> nearest x2 -> concat in front of a backbone map
+    class Route(torch.nn.Module):
+        def __init__(self):
+            super(Route, self).__init__()
+            self.conv = Conv2dUnit(64, 32, 1, stride=1, gn=1, act='leaky')
+            self.up = torch.nn.Upsample(scale_factor=2, mode='nearest')
+
+        def forward(self, x, skip):
+            return torch.cat([self.up(self.conv(x)), skip], dim=1)
+    m = Route()
+    _g23_fill(m, g)
+    x, skip = torch.randn(2, 64, 5, 7, generator=g), torch.randn(2, 32, 10, 14, generator=g)
+    out['b2_x'], out['b2_skip'] = x, skip
+    run('b2_', m, x, skip)
+    block_sd('b2_', m.conv)
+
+    # stage5's conv2: DCNv2 + gn (g2's first case: 32 channels, 9 x 9)
+    m = Conv2dUnit(32, 32, 3, stride=1, gn=1, groups=4, act='relu', use_dcn=True)
+    _g23_fill(m, g)
+    x = torch.randn(2, 32, 9, 9, generator=g)
+    out['b3_x'] = x
+    run('b3_', m, x)
+    block_sd('b3_', m)
+
+    def model_case(tag, C, S, N, bb_norm, hd_norm):
+        import copy
+        cfg = C()
+        cfg.backbone['norm_type'], cfg.head['norm_type'] = bb_norm, hd_norm
+        mm, shapes = build_ref(cfg, 0)
+        x = synth.synth_images(N, S, seed=1234)
+        im_size = torch.tensor([[480., 640.], [375., 500.]])[:N]
+        m64 = copy.deepcopy(mm).double()
+        with torch.no_grad():
+            feats = mm.backbone(x)
+            outs = mm.head._get_outputs(feats)
+            preds = mm(x, im_size)
+            f64 = m64.backbone(x.double())
+            o64 = m64.head._get_outputs(f64)
+            p64 = m64(x.double(), im_size.double())
+        arrs = {'meta': np.array([S, N, 0, 1234]), 'im_size': im_size, 'norms': np.array([bb_norm, hd_norm])}
+        for i, (f, fd) in enumerate(zip(feats, f64)):
+            arrs['feat%d' % i] = f
+            if bb_norm == 'gn':
+                arrs['feat%d_d64' % i] = (fd - f.double()).float()
+        for i, (o, od) in enumerate(zip(outs, o64)):
+            arrs['out%d' % i] = o
+            arrs['out%d_d64' % i] = (od - o.double()).float()
+        for i, (p, pd) in enumerate(zip(preds, p64)):
+            assert len(torch.unique(p[:, 1])) == p.shape[0]
+            arrs['pred%d' % i], arrs['pred%d_y64' % i] = p, pd
+        print('   %s: rows %s' % (tag, [tuple(p.shape) for p in preds]))
+        return arrs
+
+    save('g23_norm_act_blocks', **out)
+    save('g23_norm_act_r18vd_64', **model_case('r18vd_64', PPYOLO_r18vd_Config, 64, 2, 'gn', 'gn'))
+    save('g23_norm_act_r50vd_96', **model_case('r50vd_96', PPYOLO_2x_Config, 96, 1, 'affine_channel', 'gn'))
+
+
 ALL = dict(g1=g1_conv_units, g2=g2_dcn, g3=g3_coord_spp, g4=g4_decode, g5=g5_matrix_nms, g67=g6_g7_models,
-           g8=g8_preprocess, g9=g9_decode_harness, g10=g10_coco_records, g11=g11_state_dict_layout, g12=g12_train_step, g13=g13_ema, g14=g14_train_loop, g15=g15_dcn_backward, g16=g16_train_step_backbone, g17=g17_paddle_names, g18=g18_headline_sizes, g19=g19_augment)
+           g8=g8_preprocess, g9=g9_decode_harness, g10=g10_coco_records, g11=g11_state_dict_layout, g12=g12_train_step, g13=g13_ema, g14=g14_train_loop, g15=g15_dcn_backward, g16=g16_train_step_backbone, g17=g17_paddle_names, g18=g18_headline_sizes, g19=g19_augment, g23=g23_norm_act)
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
