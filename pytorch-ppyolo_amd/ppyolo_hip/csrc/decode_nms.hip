@@ -25,6 +25,8 @@
 namespace {
 
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.0f / (1.0f + expf(-v)); }
+// torch.clamp: a NaN stays a NaN (fmaxf / fminf alone return the bound)
+__device__ __forceinline__ float clamp_nan_(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
 
 // Wave-cooperative append of the lanes with `pass` set to the candidate list of image n.
 __device__ __forceinline__ void append_candidates(bool pass, float score, uint32_t idx, uint32_t *cand_key,
@@ -66,9 +68,9 @@ __device__ __forceinline__ void decode_pair(const DecodeArgs &p, float ioup_logi
         const float ioup = sigmoidf_(ioup_logit);
         const float obj = sigmoidf_(obj_logit);
         float nw = powf(obj, p.e_obj) * powf(ioup, p.e_iou);
-        nw = fminf(fmaxf(nw, 1e-7f), 1e7f);
+        nw = clamp_nan_(nw, 1e-7f, 1e7f);
         nw = 1.0f / nw - 1.0f;
-        nw = fminf(fmaxf(nw, 1e-7f), 1e7f);
+        nw = clamp_nan_(nw, 1e-7f, 1e7f);
         obj_logit = -logf(nw);
     }
     const float conf = sigmoidf_(obj_logit);
@@ -231,7 +233,7 @@ __device__ __forceinline__ void yolo_decode_body(const DecodeArgs &p, const int 
         const float *cl = vals + c * nch + off0 + a * per + 5;
         for (int k = 0; k < p.C; ++k) {
             const float lg = cl[k];
-            if (p.scores_dense || lg > bound) {
+            if (p.scores_dense || lg >= bound) {      // (>=: a logit of -inf under a negative threshold scores +0 > thr)
                 const float sc = conf * sigmoidf_(lg);
                 if (p.scores_dense) p.scores_dense[((long long)n * p.M_total + box) * p.C + k] = sc;
                 if (sc > p.thr) {
@@ -473,7 +475,7 @@ __global__ void __launch_bounds__(64 * DS_WAVES, 4) yolo_decode_stream_kernel(co
                     cf = a >= q ? cnf[q] : cf;
                 }
                 const float lg = v[i][e];
-                const bool pass = cls && lg > b;
+                const bool pass = cls && lg >= b;                             // (>=: see the staged sweep)
                 const unsigned long long bal = __ballot(pass);
                 if (bal == 0ull) continue;                                    // (the usual case)
                 if (pass) {
@@ -539,7 +541,7 @@ __global__ void __launch_bounds__(64 * DS_WAVES, 4) yolo_decode_stream_kernel(co
                             b = a >= q ? bda[q] : b;
                             cf = a >= q ? cfa[q] : cf;
                         }
-                        const bool pass = cls && cur[j] > b;
+                        const bool pass = cls && cur[j] >= b;
                         uint32_t key = 0u;
                         if (__ballot(pass) != 0ull) {
                             const float sc = cf * sigmoidf_(cur[j]);
