@@ -931,6 +931,49 @@ int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, const float
                        void *ws, size_t ws_bytes, void *stream);
 int ppy_mish_f32(float *x, int x_ld, int N, int H, int W, int C, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * GroupNorm, AffineChannel and Mish in the TRAINING step (csrc/norm_act.hip, csrc/norm_act_train.hip).  Views
+ * and alignment as above; every reduction is a double sum combined in a fixed order (no floating-point atomics, bit-identical from
+ * run to run), no call synchronises with the host, every workspace is the caller's.
+ *
+ * ppy_group_norm_train_f32: ppy_group_norm_f32 (the same three launches, the same values bit for bit, no upsampled store) that
+ * also leaves the statistics in the caller's mean [N * groups] (double) and rstd [N * groups] (float), which the caller keeps
+ * until the backward has run.  ws: PPY_GN_WS_BYTES(N, groups).
+ *
+ * ppy_group_norm_bwd_f32: given the raw x, those statistics and dy = d loss / d y:  z = gamma * xhat + beta [+ residual] is
+ * recomputed from x (never taken from y: Mish is not invertible), dz = dy * act'(z) -- relu / leaky by the sign of z, the forward's
+ * own pattern; Mish: n / (n + 2) + z * 4 e (e + 1) / (n + 2)^2 with e = exp(z), n = e (e + 2), evaluated in double; z > 20: 1 --
+ *   dbeta_c = sum dz, dgamma_c = sum dz * xhat over images and pixels;   per (image, group), m = H * W * C / groups:
+ *   A = sum gamma_c * dz, B = sum gamma_c * dz * xhat;   dx = rstd * (gamma_c * dz - A / m - xhat * B / m).
+ * dx is written; dgamma / dbeta are written (not accumulated) when param_grads != 0 and left untouched otherwise (frozen norm);
+ * dz (or NULL) receives dz, the gradient of the residual branch.  ws: ppy_group_norm_bwd_workspace_bytes, 8-byte aligned.
+ * C % groups != 0, a NULL or misaligned pointer: PPY_ERR_BAD_ARG; a short workspace: PPY_ERR_WORKSPACE; C > 2048: PPY_ERR_UNSUPPORTED.
+ *
+ * ppy_affine_act_f32: y = act(x * weight_c + bias_c [+ residual]), act any of the four -- the forward of a TRAINABLE AffineChannel
+ * unit behind its raw convolution (a frozen one is folded into the convolution's epilogue).
+ * ppy_affine_bwd_f32: z recomputed as above; dz = dy * act'(z), dweight_c = sum dz * x, dbias_c = sum dz, dx = dz * weight_c; the
+ * same param_grads / dz rules (ws is needed with param_grads only).  This is NOT ppy_bn_train_bwd_f32 with mean 0 and invstd 1,
+ * which subtracts batch means.
+ *
+ * ppy_mish_bwd_f32: dx = dy * mish'(x * scale_c + shift_c) (scale / shift NULL: 1 / 0): behind a bn + mish or af + mish unit, the
+ * pre-activation recomputed from the raw convolution output and the norm's per-channel scale and shift.  dx may alias dy. */
+int ppy_group_norm_train_f32(const float *x, int x_ld, const float *gamma, const float *beta, int groups, float eps, int act,
+                             const float *residual, int res_ld, float *y, int y_ld, int N, int H, int W, int C, double *mean,
+                             float *rstd, void *ws, size_t ws_bytes, void *stream);
+size_t ppy_group_norm_bwd_workspace_bytes(int N, int H, int W, int C, int groups);
+int ppy_group_norm_bwd_f32(const float *x, int x_ld, const double *mean, const float *rstd, const float *gamma, const float *beta,
+                           int groups, int act, const float *residual, int res_ld, const float *dy, int dy_ld, float *dx, int dx_ld,
+                           float *dz, int dz_ld, float *dgamma, float *dbeta, int param_grads, int N, int H, int W, int C, void *ws,
+                           size_t ws_bytes, void *stream);
+int ppy_affine_act_f32(const float *x, int x_ld, const float *weight, const float *bias, int act, const float *residual, int res_ld,
+                       float *y, int y_ld, int N, int H, int W, int C, void *stream);
+size_t ppy_affine_bwd_workspace_bytes(int N, int H, int W, int C);
+int ppy_affine_bwd_f32(const float *x, int x_ld, const float *weight, const float *bias, int act, const float *residual, int res_ld,
+                       const float *dy, int dy_ld, float *dx, int dx_ld, float *dz, int dz_ld, float *dweight, float *dbias,
+                       int param_grads, int N, int H, int W, int C, void *ws, size_t ws_bytes, void *stream);
+int ppy_mish_bwd_f32(const float *x, int x_ld, const float *scale, const float *shift, const float *dy, int dy_ld, float *dx, int dx_ld,
+                     int N, int H, int W, int C, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,16 @@ _PROTOS = {
     'ppy_group_norm_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_int]
                            + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
     'ppy_mish_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    'ppy_group_norm_train_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_int]
+                                 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    'ppy_group_norm_bwd_workspace_bytes': (c_size_t, [c_int] * 5),
+    'ppy_group_norm_bwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
+    'ppy_affine_act_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [c_void_p]),
+    'ppy_affine_bwd_workspace_bytes': (c_size_t, [c_int] * 4),
+    'ppy_affine_bwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                   c_void_p, c_void_p, c_int] + [c_int] * 4 + [c_void_p, c_size_t, c_void_p]),
+    'ppy_mish_bwd_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int] + [c_int] * 4 + [c_void_p]),
 }
 
 

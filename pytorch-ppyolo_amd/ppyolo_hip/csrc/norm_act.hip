@@ -10,23 +10,12 @@
 // var = E[d^2] - E[d]^2 carry no cancellation when the mean is large against the spread (raw double moments would still lose
 // mean^2 / var * 2^-53, visible in float32 from a ratio of 1e4 on), and every order of addition is fixed -- no atomics.
 #include "common.h"
+#include "norm_act.h"
 
 namespace {
 
 constexpr int GN_THREADS = 256;
 constexpr int GN_MIN_CHUNK = 32;      // pixels: below it a chunk is not worth a workgroup
-
-__device__ __forceinline__ float mish_f32(float v) {
-    if (v > 20.f) return v;                     // torch softplus threshold; tanh(v) rounds to 1 from v = 9.02 on
-    const float e = expf(v);
-    const float n = e * (e + 2.f);              // tanh(log(1 + e)) = ((1 + e)^2 - 1) / ((1 + e)^2 + 1) = n / (n + 2)
-    return v * (n / (n + 2.f));
-}
-
-__device__ __forceinline__ float norm_act(float v, int act) {
-    if (act == PPY_ACT_MISH) return mish_f32(v);
-    return ppy_apply_act(v, act);
-}
 
 // grid (nchunks, N, slabs).  Threads are (tx, ty) = (channel quad, pixel) with TX = 1 << tx_log2 <= 64 lanes along C.  slabs > 1: a
 // workgroup owns the 4 * TX channels of its slab only (whole groups: the host checks 4 * TX % (C / G) == 0), which gives the small,
@@ -171,11 +160,10 @@ int stream_grid(long long total) {          // 256 CUs x 8 workgroups of four wa
 
 bool view_ok(const void *p, int ld, int C) { return p && C > 0 && C % 4 == 0 && ld >= C && ld % 4 == 0 && ((uintptr_t)p & 15) == 0; }
 
-}  // namespace
-
-extern "C" int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, const float *beta, int groups, float eps, int act,
-                                  const float *residual, int res_ld, float *y, int y_ld, int upsample2x, int N, int H, int W, int C,
-                                  void *ws, size_t ws_bytes, void *stream) {
+// The three launches. mean [N * G] doubles and rstd [N * G] floats: inside the workspace (inference) or the caller's own (training).
+int gn_forward(const float *x, int x_ld, const float *gamma, const float *beta, int groups, float eps, int act, const float *residual,
+               int res_ld, float *y, int y_ld, int upsample2x, int N, int H, int W, int C, void *ws, size_t ws_bytes, double *mean_out,
+               float *rstd_out, bool own_stats, void *stream) {
     ppy_drop_stale_error();
     PPY_CHECK_ARG(N > 0 && H > 0 && W > 0 && view_ok(x, x_ld, C) && view_ok(y, y_ld, C));
     PPY_CHECK_ARG(gamma && beta && ((uintptr_t)gamma & 15) == 0 && ((uintptr_t)beta & 15) == 0);
@@ -183,6 +171,7 @@ extern "C" int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, 
     PPY_CHECK_ARG(groups > 0 && C % groups == 0 && eps >= 0.f);
     PPY_CHECK_ARG(act == PPY_ACT_NONE || act == PPY_ACT_RELU || act == PPY_ACT_LEAKY || act == PPY_ACT_MISH);
     PPY_CHECK_ARG((long long)N * groups < (1LL << 24) && (long long)H * W < (1LL << 30) && N < 65536);
+    PPY_CHECK_ARG(!own_stats || (mean_out && rstd_out && ((uintptr_t)mean_out & 7) == 0 && ((uintptr_t)rstd_out & 3) == 0));
     if (C > 2048) return PPY_ERR_UNSUPPORTED;
     if (!ws || ((uintptr_t)ws & 7) || ws_bytes < PPY_GN_WS_BYTES(N, groups)) return PPY_ERR_WORKSPACE;
     const int P = H * W, Q = C / 4;
@@ -193,8 +182,8 @@ extern "C" int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, 
     while ((1 << tx_log2) < Q && tx_log2 < 6) ++tx_log2;
     const long long NG = (long long)N * groups;
     double *part = static_cast<double *>(ws);                   // [N][nchunks][G][2]
-    double *mean = part + NG * PPY_GN_MAX_CHUNKS * 2;           // [N][G]
-    float *rstd = reinterpret_cast<float *>(mean + NG);         // [N][G]
+    double *mean = own_stats ? mean_out : part + NG * PPY_GN_MAX_CHUNKS * 2;           // [N][G]
+    float *rstd = own_stats ? rstd_out : reinterpret_cast<float *>(mean + NG);         // [N][G]
     const size_t lds = (size_t)(GN_THREADS * 8 + 2 * C) * sizeof(double);      // <= 48 KB
     hipStream_t st = (hipStream_t)stream;
     const int TX = 1 << tx_log2, slabs = (4 * TX) % (C / groups) == 0 ? (Q + TX - 1) / TX : 1;      // <= 8 (C <= 2048)
@@ -209,6 +198,23 @@ extern "C" int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, 
         hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(grid), dim3(GN_THREADS), 0, st, x, x_ld, gamma, beta, mean, rstd, residual, res_ld, y,
                            y_ld, N, H, W, C, groups, act);
     return ppy_launch_status();
+}
+
+}  // namespace
+
+extern "C" int ppy_group_norm_f32(const float *x, int x_ld, const float *gamma, const float *beta, int groups, float eps, int act,
+                                  const float *residual, int res_ld, float *y, int y_ld, int upsample2x, int N, int H, int W, int C,
+                                  void *ws, size_t ws_bytes, void *stream) {
+    return gn_forward(x, x_ld, gamma, beta, groups, eps, act, residual, res_ld, y, y_ld, upsample2x, N, H, W, C, ws, ws_bytes, nullptr,
+                      nullptr, false, stream);
+}
+
+// The training forward: the same three launches, the statistics left in the caller's mean / rstd for ppy_group_norm_bwd_f32.
+extern "C" int ppy_group_norm_train_f32(const float *x, int x_ld, const float *gamma, const float *beta, int groups, float eps, int act,
+                                        const float *residual, int res_ld, float *y, int y_ld, int N, int H, int W, int C, double *mean,
+                                        float *rstd, void *ws, size_t ws_bytes, void *stream) {
+    return gn_forward(x, x_ld, gamma, beta, groups, eps, act, residual, res_ld, y, y_ld, 0, N, H, W, C, ws, ws_bytes, mean, rstd, true,
+                      stream);
 }
 
 extern "C" int ppy_mish_f32(float *x, int x_ld, int N, int H, int W, int C, void *stream) {

@@ -619,6 +619,75 @@ def mish(x):
     check(lib().ppy_mish_f32(x.ptr, x.ld, x.N, x.H, x.W, x.C, _stream()), 'ppy_mish_f32')
 
 
+def _rv(v):
+    return (None, 0) if v is None else (v.ptr, v.ld)
+
+
+def group_norm_train(x, gamma, beta, groups, eps, y, mean, rstd, act=None, residual=None, ws=None):
+    """group_norm() that leaves the statistics for the backward: mean [N * groups] float64, rstd [N * groups] float32 (the caller keeps
+    them until group_norm_bwd has run).  See ppy_group_norm_train_f32."""
+    _dev(x.t, gamma, beta, y.t, mean, rstd, None if residual is None else residual.t)
+    assert (y.N, y.H, y.W, y.C) == (x.N, x.H, x.W, x.C) and gamma.numel() == x.C and beta.numel() == x.C
+    assert mean.dtype == torch.float64 and rstd.dtype == torch.float32 and mean.numel() == x.N * groups == rstd.numel()
+    assert residual is None or (residual.N, residual.H, residual.W, residual.C) == (x.N, x.H, x.W, x.C)
+    if ws is None:
+        ws = group_norm_workspace(x.N, groups, x.t.device)
+    rp, rl = _rv(residual)
+    check(lib().ppy_group_norm_train_f32(x.ptr, x.ld, gamma.data_ptr(), beta.data_ptr(), int(groups), float(eps), _lib.NORM_ACT[act], rp, rl,
+                                         y.ptr, y.ld, x.N, x.H, x.W, x.C, mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(),
+                                         ws.numel() * ws.element_size(), _stream()), 'ppy_group_norm_train_f32')
+    return ws
+
+
+def group_norm_bwd(x, mean, rstd, gamma, beta, groups, dy, dx, act=None, residual=None, dz=None, dgamma=None, dbeta=None, ws=None):
+    """x, dy, dx, residual, dz: View.  dgamma / dbeta None: a frozen norm (nothing is written for them).  See ppy_group_norm_bwd_f32."""
+    _dev(x.t, mean, rstd, gamma, beta, dy.t, dx.t, dgamma, dbeta, None if residual is None else residual.t, None if dz is None else dz.t)
+    assert (dgamma is None) == (dbeta is None)
+    for v in (dy, dx, residual, dz):
+        assert v is None or (v.N, v.H, v.W, v.C) == (x.N, x.H, x.W, x.C)
+    ws = _ws_for(int(lib().ppy_group_norm_bwd_workspace_bytes(x.N, x.H, x.W, x.C, int(groups))), ws, x.t.device)
+    rp, rl = _rv(residual)
+    zp, zl = _rv(dz)
+    check(lib().ppy_group_norm_bwd_f32(x.ptr, x.ld, mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(), int(groups),
+                                       _lib.NORM_ACT[act], rp, rl, dy.ptr, dy.ld, dx.ptr, dx.ld, zp, zl, _p(dgamma), _p(dbeta),
+                                       int(dgamma is not None), x.N, x.H, x.W, x.C, ws.data_ptr(), ws.numel() * ws.element_size(),
+                                       _stream()), 'ppy_group_norm_bwd_f32')
+    return ws
+
+
+def affine_act(x, weight, bias, y, act=None, residual=None):
+    """y = act(x * weight + bias [+ residual]) per channel (ppy_affine_act_f32): a trainable AffineChannel unit's forward."""
+    _dev(x.t, weight, bias, y.t, None if residual is None else residual.t)
+    assert (y.N, y.H, y.W, y.C) == (x.N, x.H, x.W, x.C) and weight.numel() == x.C == bias.numel()
+    rp, rl = _rv(residual)
+    check(lib().ppy_affine_act_f32(x.ptr, x.ld, weight.data_ptr(), bias.data_ptr(), _lib.NORM_ACT[act], rp, rl, y.ptr, y.ld, x.N, x.H, x.W,
+                                   x.C, _stream()), 'ppy_affine_act_f32')
+
+
+def affine_bwd(x, weight, bias, dy, dx, act=None, residual=None, dz=None, dweight=None, dbias=None, ws=None):
+    """Backward of affine_act; dweight / dbias None: frozen.  See ppy_affine_bwd_f32."""
+    _dev(x.t, weight, bias, dy.t, dx.t, dweight, dbias, None if residual is None else residual.t, None if dz is None else dz.t)
+    assert (dweight is None) == (dbias is None)
+    for v in (dy, dx, residual, dz):
+        assert v is None or (v.N, v.H, v.W, v.C) == (x.N, x.H, x.W, x.C)
+    if dweight is not None:
+        ws = _ws_for(int(lib().ppy_affine_bwd_workspace_bytes(x.N, x.H, x.W, x.C)), ws, x.t.device)
+    rp, rl = _rv(residual)
+    zp, zl = _rv(dz)
+    check(lib().ppy_affine_bwd_f32(x.ptr, x.ld, weight.data_ptr(), bias.data_ptr(), _lib.NORM_ACT[act], rp, rl, dy.ptr, dy.ld, dx.ptr, dx.ld,
+                                   zp, zl, _p(dweight), _p(dbias), int(dweight is not None), x.N, x.H, x.W, x.C, _p(ws),
+                                   0 if ws is None else ws.numel() * ws.element_size(), _stream()), 'ppy_affine_bwd_f32')
+    return ws
+
+
+def mish_bwd(x, dy, dx, scale=None, shift=None):
+    """dx = dy * mish'(x * scale + shift) per channel (ppy_mish_bwd_f32); dx may be dy."""
+    _dev(x.t, dy.t, dx.t, scale, shift)
+    assert (dy.N, dy.H, dy.W, dy.C) == (x.N, x.H, x.W, x.C) == (dx.N, dx.H, dx.W, dx.C)
+    check(lib().ppy_mish_bwd_f32(x.ptr, x.ld, _p(scale), _p(shift), dy.ptr, dy.ld, dx.ptr, dx.ld, x.N, x.H, x.W, x.C, _stream()),
+          'ppy_mish_bwd_f32')
+
+
 def spp(x, y5, y9, y13):
     _dev(x.t, y5.t)
     assert y5.ld == y9.ld == y13.ld

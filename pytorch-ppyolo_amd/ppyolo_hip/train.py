@@ -25,6 +25,7 @@ import warnings
 import torch
 
 from . import ops as K
+from . import train_norm as TN
 from . import train_plan as TP
 from ._lib import PPYoloHipError, conv_cfg, conv_cfgs
 
@@ -146,7 +147,7 @@ class TrainStep(object):
         dev = next(model.parameters()).device
         if dev.type != 'cuda':
             raise PPYoloHipError('the training step needs the model on a ROCm device (got %s); there is no CPU path' % dev)
-        check_bn_only(model)
+        self._gn = TN.norm_units(model)          # GroupNorm / AffineChannel / Mish units train too (csrc/norm_act_train.hip)
         cfg = ModelSettings(model) if cfg is None else cfg
         self.freeze_at = int(cfg.backbone.get('freeze_at', 5))
         if not 0 <= self.freeze_at <= 5:
@@ -428,12 +429,18 @@ class TrainStep(object):
         pad = (R - 1) // 2
         Ho, Wo = K.conv_out_hw(xin.H, xin.W, R, S, stride, pad)
         bias = self.param(prefix + '.conv.bias')
-        has_bn = prefix + '.bn.weight' in sd
+        nform = TP.norm_form(TP.norm_of(sd, prefix), act, trainable)      # what follows the convolution (train_plan.norm_form)
+        if nform in ('af_fold', 'af_fold_mish'):
+            return TN.af_folded_unit(self, prefix, x, xin, ent, stride, pad, act, res, out, coord_out, (Ho, Wo))
+        has_bn = nform in ('bn', 'bn_mish')
+        has_norm = nform != 'none'
+        if nform == 'bn_mish' and res is not None:
+            raise PPYoloHipError('%s: BatchNorm + Mish with a residual is not implemented in the training step' % prefix)
         raw_box = []
 
         def get_raw():          # (allocated on first use: a layer whose BatchNorm is applied from the convolution's epilogue never stores it)
             if not raw_box:
-                raw_box.append(self.new(xin.N, Ho, Wo, Kout, ld=TP.r32(Kout) if not has_bn else None, req=trainable, zero=not has_bn))
+                raw_box.append(self.new(xin.N, Ho, Wo, Kout, ld=TP.r32(Kout) if not has_norm else None, req=trainable, zero=not has_norm))
             return raw_box[0]
         one, b0 = self._vec('one', Kout, 1.0), bias if bias is not None else self._vec('zero', Kout, 0.0)
         use_f16 = self.f16 and xin.amax is not None and ent['f16'] is not None
@@ -460,11 +467,20 @@ class TrainStep(object):
             run(cfg_id, splitk)
         cur.flops += 2 * xin.N * Ho * Wo * Kout * R * S * ent['Cin']
         raw = None if epi else get_raw()
-        y, mean, invstd = (self._bn_fwd(prefix, raw, slices, (xin.N, Ho, Wo, Kout), trainable, act, res, out, coord_out, epi) if has_bn
-                           else (raw, None, None))
+        nctx = None
+        if nform == 'bn':
+            y, mean, invstd = self._bn_fwd(prefix, raw, slices, (xin.N, Ho, Wo, Kout), trainable, act, res, out, coord_out, epi)
+        elif nform == 'bn_mish':      # BatchNorm with act = None, Mish in place (|mish(v)| <= |v|: the tracked maximum stays an upper bound)
+            y, mean, invstd = self._bn_fwd(prefix, raw, slices, (xin.N, Ho, Wo, Kout), trainable, None, None, out, coord_out, epi)
+            TN.mish_inplace(y)
+            nctx = ('bn_mish',)
+        elif has_norm:
+            (y, nctx), mean, invstd = TN.post_fwd(self, prefix, nform, raw, trainable, act, res, out, coord_out), None, None
+        else:
+            y, mean, invstd = raw, None, None
         if trainable:
             def bwd_unit():
-                self._conv_unit_bwd(prefix, x, xin, raw, y, mean, invstd, act, stride, pad, ent, res)
+                self._conv_unit_bwd(prefix, x, xin, raw, y, mean, invstd, act, stride, pad, ent, res, nctx)
                 self._grads_done(prefix)
             cur.tape.append(bwd_unit)
         if self.acts is not None:          # debugging / tests: activations (and, after the backward, their gradients) by layer
@@ -577,11 +593,11 @@ class TrainStep(object):
             self._wpending = False
         self._wkeep = []
 
-    def _conv_unit_bwd(self, prefix, x, xin, raw, y, mean, invstd, act, stride, pad, ent, res=None):
+    def _conv_unit_bwd(self, prefix, x, xin, raw, y, mean, invstd, act, stride, pad, ent, res=None, nctx=None):
         dy = y.g
         if dy is None:
             raise PPYoloHipError('%s: no gradient reached this layer' % prefix)
-        if res is not None:
+        if res is not None and nctx is None:
             # y = act(bn(conv) + res): the gradient in front of the activation goes to both branches
             dz = self.new(y.N, y.H, y.W, y.C)
             K.act_bwd(dy.view(), y.view(), dz.view(), act)
@@ -589,7 +605,9 @@ class TrainStep(object):
                 self.accum(res, dz)
             dy, act = dz, None
         f16 = self.f16 and xin.amax is not None       # weight gradient on the f16x2 kernel: both operands' maxima are tracked
-        if mean is not None:
+        if nctx is not None:
+            d_raw = TN.post_bwd(self, prefix, nctx, raw, y, dy, act, res, mean, invstd, track=f16)
+        elif mean is not None:
             d_raw = self._bn_bwd(prefix, raw, y, dy, mean, invstd, act, track=f16)
         else:
             d_raw = dy
@@ -626,20 +644,37 @@ class TrainStep(object):
                         None, ws=self.cur.ws, w_x3=None if self.fp32 else self._planes(co))
         w = self.weight(prefix + '.conv.dcn_weight')
         Kout = w['krsc'].shape[0]
-        raw = self.new(x.N, Ho, Wo, Kout)
-        use_f16 = self.f16 and x.amax is not None and w['f16'] is not None
+        nform = TP.norm_form(TP.norm_of(self.sd, prefix), act, trainable)
+        if nform == 'none':
+            raise PPYoloHipError('%s: a deformable unit without a norm is not implemented in the training step' % prefix)
+        fold = nform in ('af_fold', 'af_fold_mish')      # a frozen AffineChannel: scale, shift and activation in the kernel's epilogue
+        if fold and x.req:
+            raise PPYoloHipError('%s: a frozen AffineChannel unit above a trainable layer is not implemented' % prefix)
+        raw = TN.dest(self, prefix, (x.N, Ho, Wo, Kout), False, None, False) if fold else self.new(x.N, Ho, Wo, Kout)
+        use_f16 = self.f16 and x.amax is not None and w['f16'] is not None and not fold
         ent = (self._tuned_f if use_f16 else self._tuned).get(TP.shape_key('dcnf', x.N, x.H, x.W, x.C, Kout, 3, stride, f=use_f16))
-        K.dcnv2(x.view(), w['krsc'], self._vec('one', Kout, 1.0), self._vec('zero', Kout, 0.0), om.view(), raw.view(), stride, 1, None,
+        scale, shift = (TN.af_scale_shift(self, prefix, Kout, self.sd.get(prefix + '.conv.dcn_bias')) if fold
+                        else (self._vec('one', Kout, 1.0), self._vec('zero', Kout, 0.0)))
+        K.dcnv2(x.view(), w['krsc'], scale, shift, om.view(), raw.view(), stride, 1, (None if act == 'mish' else act) if fold else None,
                 self.cur.ws, cfg=ent[0] if (ent and not self.fp32) else -1, splitk=ent[1] if (ent and not self.fp32) else 0,
                 w_x3=None if (use_f16 or self.fp32) else self._planes(w), w_f16=w['f16'] if use_f16 else None,
                 amax_in=x.amax if use_f16 else None)
         self.cur.flops += 2 * x.N * Ho * Wo * (Kout * 9 * x.C + 27 * 9 * x.C)
-        y, mean, invstd = self._bn_fwd(prefix, raw, 0, (x.N, Ho, Wo, Kout), trainable, act)
+        if fold:
+            if act == 'mish':
+                TN.mish_inplace(raw)
+            return raw
+        nctx = None
+        if nform == 'bn':
+            y, mean, invstd = self._bn_fwd(prefix, raw, 0, (x.N, Ho, Wo, Kout), trainable, act)
+        else:
+            (y, nctx), mean, invstd = TN.post_fwd(self, prefix, nform, raw, trainable, act), None, None
 
         def bwd():
             if y.g is None:
                 raise PPYoloHipError('%s: no gradient reached this layer' % prefix)
-            d_raw = self._bn_bwd(prefix, raw, y, y.g, mean, invstd, act, track=False)
+            d_raw = (self._bn_bwd(prefix, raw, y, y.g, mean, invstd, act, track=False) if nctx is None
+                     else TN.post_bwd(self, prefix, nctx, raw, y, y.g, act))
             dxs = self.new(x.N, x.H, x.W, x.C)
             d_om = self.new(x.N, Ho, Wo, 27, ld=32, zero=True)
             K.dcnv2_backward(x.view(), w['krsc'], om.view(), d_raw.view(), dxs.view(), d_om.view(), self.G[prefix + '.conv.dcn_weight'],
@@ -672,13 +707,24 @@ class TrainStep(object):
         N, _, H, W = x_nchw.shape
         Ho, Wo = K.conv_out_hw(H, W, 3, 3, 2, 1)
         Kout = ent['krsc'].shape[0]
-        raw = self.new(N, Ho, Wo, Kout)
-        K.stem_conv(x_nchw, ent['krsc'][..., :3].permute(0, 3, 1, 2).contiguous(), self._vec('one', Kout, 1.0), self._vec('zero', Kout, 0.0),
-                    raw.view(), None)
-        y0, mean, invstd = self._bn_fwd(p, raw, 0, (N, Ho, Wo, Kout), trainable, 'relu')
+        nform = TP.norm_form(TP.norm_of(self.sd, p), 'relu', trainable)
+        fold = nform == 'af_fold'                              # a frozen AffineChannel: scale, shift and relu in the stem kernel's epilogue
+        raw = TN.dest(self, p, (N, Ho, Wo, Kout), False, None, False) if fold else self.new(N, Ho, Wo, Kout)
+        cb = self.sd.get(p + '.conv.bias')
+        scale, shift = (TN.af_scale_shift(self, p, Kout, cb) if fold
+                        else (self._vec('one', Kout, 1.0), self._vec('zero', Kout, 0.0) if (cb is None or nform == 'bn') else self.param(p + '.conv.bias')))
+        K.stem_conv(x_nchw, ent['krsc'][..., :3].permute(0, 3, 1, 2).contiguous(), scale, shift, raw.view(), 'relu' if fold else None)
+        nctx = None
+        if fold:
+            y0 = raw
+        elif nform == 'bn':
+            y0, mean, invstd = self._bn_fwd(p, raw, 0, (N, Ho, Wo, Kout), trainable, 'relu')
+        else:
+            (y0, nctx), mean, invstd = TN.post_fwd(self, p, nform, raw, trainable, 'relu'), None, None
         if trainable:                                          # freeze_at = 0: the first convolution's weight gradient (no data gradient: the image)
             def bwd():
-                d_raw = self._bn_bwd(p, raw, y0, y0.g, mean, invstd, 'relu', track=False)
+                d_raw = (self._bn_bwd(p, raw, y0, y0.g, mean, invstd, 'relu', track=False) if nctx is None
+                         else TN.post_bwd(self, p, nctx, raw, y0, y0.g, 'relu'))
                 x4 = torch.zeros((N, H, W, 4), dtype=torch.float32, device=self.dev)
                 x4[..., :3] = x_nchw.permute(0, 2, 3, 1)
                 dw3 = torch.empty((Kout, 3, 3, 3), dtype=torch.float32, device=self.dev)

@@ -109,6 +109,60 @@ def conv_form(has_bn, f16, trainable, coord, R, S, stride, C, Kout, HW, table, s
     return 'plain', cfg, splitk
 
 
+NORMS = ('bn', 'gn', 'af')                 # the state_dict's sub-module names: BatchNorm2d, GroupNorm, AffineChannel
+GN_MAX_CHANNELS = 2048                     # ppy_group_norm_f32 / _bwd_f32: PPY_ERR_UNSUPPORTED above
+
+
+def norm_of(keys, prefix):
+    """Which norm a Conv2dUnit holds, read from its state_dict keys ('<prefix>.bn.weight' ...): 'bn' / 'gn' / 'af' / None."""
+    for n in NORMS:
+        if '%s.%s.weight' % (prefix, n) in keys:
+            return n
+    return None
+
+
+def norm_form(norm, act, trainable):
+    """How the training forward and backward of a unit run behind its convolution, beside conv_form (which keeps deciding how the
+    convolution of a 'bn' unit runs).  norm: norm_of(); act: None / 'relu' / 'leaky' / 'mish'; trainable: its parameters train.
+      'none':         no norm: the convolution with its bias (the output convolutions);
+      'bn':           BatchNorm on batch statistics + relu / leaky / nothing: train.hip, exactly as before;
+      'bn_mish':      BatchNorm with act = None, then Mish in place; backward: Mish backward (pre-activation recomputed from the raw
+                      output and the batch scale / shift), then the BatchNorm backward with act = None;
+      'gn':           raw convolution (scale 1, shift = conv bias), GroupNorm training forward (any activation, the residual inside);
+                      backward: GroupNorm backward, then the convolution's weight / data gradients;
+      'af_fold':      frozen AffineChannel: (af.weight, af.bias + conv_bias * af.weight) and the activation in the convolution's own
+                      epilogue, no extra launch -- the inference path's fold;
+      'af_fold_mish': ... Mish cannot go into the epilogue: it follows as a launch;
+      'af_train':     trainable AffineChannel: raw convolution, one apply launch (any activation), the AffineChannel backward."""
+    if act not in (None, 'relu', 'leaky', 'mish'):
+        raise ValueError('activation %r' % (act,))
+    if norm is None:
+        if act == 'mish':
+            raise ValueError('Mish behind a convolution without a norm is not implemented in the training step')
+        return 'none'
+    if norm == 'bn':
+        return 'bn_mish' if act == 'mish' else 'bn'
+    if norm == 'gn':
+        return 'gn'
+    if norm == 'af':
+        return 'af_train' if trainable else ('af_fold_mish' if act == 'mish' else 'af_fold')
+    raise ValueError('norm %r' % (norm,))
+
+
+def norm_refusal(name, norm, channels, groups, norm_decay):
+    """Why the training step refuses a GroupNorm / AffineChannel unit, by its name -- or None."""
+    if norm not in ('gn', 'af'):
+        return None
+    if norm == 'gn' and (groups <= 0 or channels % groups != 0):
+        return '%s: GroupNorm of %d channels in %d groups (C %% groups != 0)' % (name, channels, groups)
+    if norm == 'gn' and channels > GN_MAX_CHANNELS:
+        return '%s: GroupNorm of %d channels: the kernels implement C <= %d' % (name, channels, GN_MAX_CHANNELS)
+    if float(norm_decay) != 0.0:
+        return ('%s: norm_decay = %r: norm scales / offsets are stepped without weight decay (every configuration has 0)'
+                % (name, norm_decay))
+    return None
+
+
 def kernel_shape(shape):
     """A parameter's shape in kernel layout: a convolution weight [K, C, R, S] is kept KRSC with C padded to a multiple of 32 (the
     stem's 3 channels, a CoordConv's C + 2); everything else as the state_dict has it."""
@@ -118,7 +172,8 @@ def kernel_shape(shape):
 def flat_layout(keyed_shapes):
     """[(key, kernel-layout shape)] of the trainable tensors, in state_dict order -> ({key: (offset, numel, shape)}, total, n_decay).
     Convolution weights first, then the conv_offset biases (the reference decays them like a weight: custom_layers.py:189-194) --
-    [0, n_decay) is the weight-decay group -- then biases and BatchNorm scales / offsets; every tensor padded to 64 floats."""
+    [0, n_decay) is the weight-decay group -- then biases and the scales / offsets of BatchNorm, GroupNorm and AffineChannel
+    ('.bn.' / '.gn.' / '.af.' + 'weight' / 'bias': no decay, reference custom_layers.py:216-241); every tensor padded to 64 floats."""
     convs = [(k, s) for k, s in keyed_shapes if len(s) == 4] + [(k, s) for k, s in keyed_shapes if k.endswith('.conv_offset.bias')]
     rest = [(k, s) for k, s in keyed_shapes if len(s) != 4 and not k.endswith('.conv_offset.bias')]
     offs, total, n_decay = {}, 0, 0
@@ -150,7 +205,7 @@ def bucket_of(key):
 def unit_of(key):
     """The Conv2dUnit prefix a parameter key belongs to ('....conv.weight' / '.bn.bias' / '.conv.conv_offset.bias' ...)."""
     for tail in ('.conv.conv_offset.weight', '.conv.conv_offset.bias', '.conv.dcn_weight', '.conv.weight', '.conv.bias', '.bn.weight',
-                 '.bn.bias'):
+                 '.bn.bias', '.gn.weight', '.gn.bias', '.af.weight', '.af.bias'):
         if key.endswith(tail):
             return key[:-len(tail)]
     return key
