@@ -408,6 +408,46 @@ int ppy_preprocess_u8_f32(int n, const unsigned char *const *images, const int *
                           const int *row_stride, int swap_rb, int S, const float *lut /* device [3][256] */,
                           float *out, void *stream);
 
+/* Pillow's resize on the device, bit for bit (csrc/pil_resize.hip): the reference's
+ * ResizeImage(use_cv2=False) (tools/transform.py:1016-1024) = Image.fromarray(u8_hwc).resize((ow, oh), filter) for 3-channel
+ * uint8 images as Pillow 12.2.0 computes it.  filter is PILLOW's code: 0 NEAREST, 1 LANCZOS, 2 BILINEAR, 3 BICUBIC, 4 BOX,
+ * 5 HAMMING.  Filters 1..5 are two separable passes, horizontal first, through a uint8 intermediate of h rows x ow columns,
+ * each clip8((2^21 + sum pixel * k) >> 22) in int32 with k = round(w * 2^22) of the normalised double weights; a pass whose
+ * axis keeps its size is skipped; NEAREST is an index map per axis.
+ *
+ * ppy_pil_resize_plan (HOST only, no GPU call): validates the batch and writes the launch's blob into caller-owned host
+ * memory (8-byte aligned, blob_bytes >= ppy_pil_resize_plan_bytes of the same arguments, else PPY_ERR_WORKSPACE): a 64-byte
+ * header (the ints magic "PIL1", n, ow, oh, filter, number of tables, tallest image of the horizontal launch, bytes per row of
+ * the intermediates; the long longs blob bytes, workspace bytes; the ints descriptor offset, first table offset), n 48-byte
+ * descriptors (base, pitch, h, w, byte offset of the horizontal table or -1 when that pass is skipped, byte offset of the
+ * vertical table, offset of the intermediate in the workspace) and ONE table per distinct (in, out) axis of the batch, shared
+ * between images: the ints in, out, ksize, kind (the filter code; -1: the identity map of an axis that keeps its size), then
+ * bounds[out][2] = (first source index, taps), then k[out][ksize].  ksize = 0 marks an index map: bounds[.][0] is the source
+ * index.  *ws_bytes (may be NULL) receives the size of the device workspace the launches need (the intermediates).
+ * h_images[i].base is a DEVICE pointer (it is only copied into the descriptor): h x w pixels of 3 bytes, `pitch` bytes per row.
+ * Limits, refused and never clamped (PPY_ERR_UNSUPPORTED; h_reason, NULL or 96 chars, names the value): an input side
+ * outside 1..65535, an output side outside 1..8192, ksize > 1024, a filter outside 0..5.  n outside 1..1024, a null base or a
+ * pitch below 3 * w: PPY_ERR_BAD_ARG.  ppy_pil_resize_plan_bytes returns 0 for a batch the planner refuses.
+ *
+ * The launches (two kernels on `stream`, or one when no image changes its width; no host synchronisation): h_blob is the
+ * planner's blob on the HOST, blob its DEVICE copy (blob_bytes each), ws the device workspace.  TRUST BOUNDARY: the host blob is
+ * validated and sizes the grids, the kernels read the device copy without further checks.
+ *   ppy_pil_resize_u8          out: device uint8 [n][oh][ow][3].
+ *   ppy_preprocess_pil_u8_f32  out: device float32 [n][3][oh][ow], 16-byte aligned: channel c of the output is
+ *                              lut[c][v] of source channel (swap_rb ? 2 - c : c), as ppy_preprocess_u8_f32 stores it. */
+typedef struct ppy_pil_image_t {
+    const unsigned char *base;
+    long long pitch;                  /* bytes per row */
+    int h, w;
+} ppy_pil_image_t;
+size_t ppy_pil_resize_plan_bytes(int n, const ppy_pil_image_t *h_images, int ow, int oh, int filter);
+int ppy_pil_resize_plan(int n, const ppy_pil_image_t *h_images, int ow, int oh, int filter, void *h_blob, size_t blob_bytes,
+                        size_t *ws_bytes, char *h_reason);
+int ppy_pil_resize_u8(int n, const void *h_blob, const void *blob, size_t blob_bytes, void *ws, size_t ws_bytes,
+                      unsigned char *out, void *stream);
+int ppy_preprocess_pil_u8_f32(int n, const void *h_blob, const void *blob, size_t blob_bytes, void *ws, size_t ws_bytes,
+                              int swap_rb, const float *lut /* device [3][256] */, float *out, void *stream);
+
 /* Training batches (ppyolo_hip/augment.py TrainBatchBuilder): the reference's training reader (train.py:36-152) with
  * the transforms of config/ppyolo_2x.py:154-251, planned on the host.  blob: DEVICE copy of the planner's upload (8-byte
  * aligned, blob_bytes long): n per-sample descriptors (augment.hip struct AugSample, 328 bytes each) at offset 0, then

@@ -87,6 +87,13 @@ class DrawImage(ctypes.Structure):
     _fields_ = [('base', c_void_p), ('pitch', c_longlong), ('h', c_int), ('w', c_int)]
 
 
+class PilImage(ctypes.Structure):
+    """ppy_pil_image_t (include/ppyolo_hip.h)."""
+    _fields_ = [('base', c_void_p), ('pitch', c_longlong), ('h', c_int), ('w', c_int)]
+
+
+PIL_FILTERS = {0: 'nearest', 1: 'lanczos', 2: 'bilinear', 3: 'bicubic', 4: 'box', 5: 'hamming'}      # Pillow's codes (ppy_pil_resize_plan)
+
 DRAW_MAX_ROWS, DRAW_NAME_MAX = 1024, 64      # K and name length ppy_draw_detections_u8 takes (include/ppyolo_hip.h)
 
 _PROTOS = {
@@ -160,6 +167,11 @@ _PROTOS = {
                                                 c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     'ppy_preprocess_u8_f32': (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p]),
+    'ppy_pil_resize_plan_bytes': (c_size_t, [c_int, ctypes.POINTER(PilImage), c_int, c_int, c_int]),
+    'ppy_pil_resize_plan': (c_int, [c_int, ctypes.POINTER(PilImage), c_int, c_int, c_int, c_void_p, c_size_t, ctypes.POINTER(c_size_t),
+                                    ctypes.c_char_p]),
+    'ppy_pil_resize_u8': (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'ppy_preprocess_pil_u8_f32': (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
     'ppy_augment_render_f32': (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int, c_void_p,
                                         c_void_p]),
     'ppy_augment_canvas': (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

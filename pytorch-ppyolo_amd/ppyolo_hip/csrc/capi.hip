@@ -1,7 +1,7 @@
 // Version / error-string entry points of libppyolo_hip.so.
 #include "common.h"
 
-extern "C" int ppy_version(void) { return 102; }
+extern "C" int ppy_version(void) { return 103; }
 
 extern "C" const char *ppy_error_string(int code) {
     switch (code) {

@@ -529,6 +529,52 @@ def preprocess_images(images_u8, target_size, lut, out, swap_rb=True):
         int(bool(swap_rb)), int(target_size), lut.data_ptr(), out.data_ptr(), _stream()), 'ppy_preprocess_u8_f32')
 
 
+def pil_resize_plan(images, ow, oh, filter, alloc):
+    """The host planner of Pillow's resize (ppy_pil_resize_plan; no GPU call): images = list of (base, pitch, h, w) with `base`
+    a device address, filter = Pillow's code 0..5.  alloc(nbytes) -> address of at least nbytes of caller-owned host memory,
+    8-byte aligned, which receives the blob.  Returns (blob bytes, device workspace bytes).  A batch outside the limits raises
+    with the planner's reason, which names the value."""
+    n = len(images)
+    descs = (_lib.PilImage * max(n, 1))()
+    for d, (base, pitch, h, w) in zip(descs, images):
+        d.base, d.pitch, d.h, d.w = int(base), int(pitch), int(h), int(w)
+    reason = ctypes.create_string_buffer(96)
+    nbytes = lib().ppy_pil_resize_plan_bytes(n, descs, int(ow), int(oh), int(filter))
+    ws_bytes = ctypes.c_size_t(0)
+    rc = lib().ppy_pil_resize_plan(n, descs, int(ow), int(oh), int(filter), alloc(nbytes) if nbytes else None, nbytes,
+                                   ctypes.byref(ws_bytes), reason)
+    if rc != _lib.OK and reason.value:
+        raise _lib.PPYoloHipError('ppy_pil_resize_plan refused the batch: %s (code %d)' % (reason.value.decode(), rc))
+    check(rc, 'ppy_pil_resize_plan')
+    return nbytes, ws_bytes.value
+
+
+def _pil_launch_args(n, blob, nbytes, ws, out):
+    _dev(blob, ws, out)
+    assert blob.dtype == torch.uint8 and blob.is_contiguous() and blob.numel() >= nbytes and blob.data_ptr() % 8 == 0
+    assert ws is None or (ws.dtype == torch.uint8 and ws.is_contiguous())
+    assert out.is_contiguous() and out.shape[0] == n
+    return (0, 0) if ws is None else (ws.data_ptr(), ws.numel())
+
+
+def pil_resize_u8(n, h_blob, blob, nbytes, ws, out):
+    """Pillow's resize, store (a): h_blob = host address of the planner's blob, blob = its device copy, ws = device uint8
+    workspace (None when the plan needs none), out = device uint8 [n, oh, ow, 3]."""
+    wp, wn = _pil_launch_args(n, blob, nbytes, ws, out)
+    assert out.dtype == torch.uint8 and out.dim() == 4 and out.shape[3] == 3
+    check(lib().ppy_pil_resize_u8(n, h_blob, blob.data_ptr(), nbytes, wp, wn, out.data_ptr(), _stream()), 'ppy_pil_resize_u8')
+
+
+def preprocess_pil_images(n, h_blob, blob, nbytes, ws, lut, out, swap_rb=True):
+    """Pillow's resize, store (b): out = device float32 [n, 3, oh, ow] through lut [3,256] (normalisation_table)."""
+    wp, wn = _pil_launch_args(n, blob, nbytes, ws, out)
+    _dev(lut)
+    assert out.dtype == torch.float32 and out.dim() == 4 and out.shape[1] == 3
+    assert lut.dtype == torch.float32 and lut.is_contiguous() and tuple(lut.shape) == (3, 256)
+    check(lib().ppy_preprocess_pil_u8_f32(n, h_blob, blob.data_ptr(), nbytes, wp, wn, int(bool(swap_rb)), lut.data_ptr(), out.data_ptr(),
+                                          _stream()), 'ppy_preprocess_pil_u8_f32')
+
+
 def _augment_sources(blob, sources):
     """The host arrays (n_src, ptrs, pitch, h, w) of ppy_augment_*_src for a list of uint8 [h,w,3] device tensors: pixel stride 3,
     any row pitch >= 3 * w, any alignment (a view `big[3:3+h, 5:5+w]` is a source as it lies)."""

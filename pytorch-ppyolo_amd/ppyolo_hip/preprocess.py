@@ -3,7 +3,11 @@
 The resize runs in the HIP kernel (csrc/preprocess.hip).  The numpy normalisation of the reference
 (tools/transform.py:895-917: `im.astype(float32) / 255.0`, `im -= mean`, `im /= std` with float64 mean / std) is a
 function of (grey level, channel); it is tabulated here with that very numpy expression, so the kernel's output is the
-reference's float32 bit for bit whatever numpy's promotion rules do."""
+reference's float32 bit for bit whatever numpy's promotion rules do.
+
+`resizeImage['use_cv2'] = False` selects the reference's other branch (tools/transform.py:1016-1024): Pillow's
+`Image.resize((S, S), interp)` with `interp` one of PILLOW's filter codes, bit for bit on the device (csrc/pil_resize.hip,
+ppyolo_hip/resize.py) in front of the same table and the same store."""
 import numpy as np
 import torch
 
@@ -32,7 +36,18 @@ class Preprocessor(object):
         n = cfg.normalizeImage
         if n.get('is_channel_first', False) or not cfg.permute.get('channel_first', True) or cfg.permute.get('to_bgr', False):
             raise PPYoloHipError('only the reference inference layout is implemented: HWC normalise, CHW output, RGB')
-        if cfg.resizeImage.get('interp', 2) != 2:
+        r = cfg.resizeImage
+        if r.get('max_size', 0) != 0:      # the reference raises on the PIL branch; keep-ratio is not implemented on the cv2 one
+            raise PPYoloHipError('resizeImage max_size=%r: keep-ratio resizing (max_size != 0) is not implemented' % (r['max_size'],))
+        use_cv2 = r.get('use_cv2', True)
+        self._pil = None
+        if use_cv2 == False:      # noqa: E712 (the reference's own switch, `if self.use_cv2:` -- False, or 0)
+            # reference tools/transform.py:1016-1024: Image.fromarray(im).resize((S, S), interp), interp = PILLOW's filter code
+            from .resize import PilPlanner, check_filter
+            self._pil = PilPlanner(check_filter(r.get('interp', 2), 'resizeImage use_cv2=False interp'), device)
+        elif use_cv2 != True:      # noqa: E712
+            raise PPYoloHipError('resizeImage use_cv2=%r: expected True (cv2.resize) or False (PIL.Image.resize)' % (use_cv2,))
+        elif r.get('interp', 2) != 2:
             raise PPYoloHipError('only cv2.INTER_CUBIC (interp=2), the reference configs\' setting, is implemented')
         self.S = int(target_size)
         self.to_rgb = bool(cfg.decodeImage['to_rgb'])
@@ -53,6 +68,11 @@ class Preprocessor(object):
         n = len(dev)
         if out is None:
             out = torch.empty((n, 3, self.S, self.S), dtype=torch.float32, device=self.device)
-        ops.preprocess_images(dev, self.S, self.lut, out, swap_rb=self.to_rgb)
+        if self._pil is not None:      # the planner keeps its blob, its workspace and `dev` alive across the two launches
+            np_, h_blob, blob, nbytes, ws = self._pil.plan(dev, self.S, self.S)
+            assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n, 3, self.S, self.S)
+            ops.preprocess_pil_images(np_, h_blob, blob, nbytes, ws, self.lut, out, swap_rb=self.to_rgb)
+        else:
+            ops.preprocess_images(dev, self.S, self.lut, out, swap_rb=self.to_rgb)
         im_size = torch.tensor([[d.shape[0], d.shape[1]] for d in dev], dtype=torch.float32).to(self.device, non_blocking=True)
         return out, im_size

@@ -1,0 +1,158 @@
+"""Pillow's `Image.resize` on the device, bit for bit (csrc/pil_resize.hip).
+
+    from ppyolo_hip.resize import PilResizer, BICUBIC
+    thumbs = PilResizer(BICUBIC)(images, size=(160, 120))      # list of uint8 [120, 160, 3] device tensors
+
+The coefficient tables are planned in the library (ppy_pil_resize_plan, C++ on the host: nothing per image is built in the
+interpreter), one per distinct axis of the batch, and cross to the device in one copy out of a pinned buffer this object owns;
+the intermediate images of the two-pass filters live in a device workspace it owns too.  Both grow on demand."""
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import PPYoloHipError
+
+NEAREST, LANCZOS, BILINEAR, BICUBIC, BOX, HAMMING = range(6)      # Pillow's codes, the ones the reference's `interp` carries
+
+
+def check_filter(filter, what='filter'):
+    if isinstance(filter, bool) or not isinstance(filter, (int, np.integer)) or int(filter) not in _lib.PIL_FILTERS:
+        raise PPYoloHipError('%s=%r: expected one of Pillow\'s filter codes %s' % (
+            what, filter, ', '.join('%d %s' % kv for kv in sorted(_lib.PIL_FILTERS.items()))))
+    return int(filter)
+
+
+def _same_device(a, b):
+    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
+
+
+class PilPlanner(object):
+    """The host half of a launch, shared by PilResizer and Preprocessor: plans a batch into the pinned staging buffer, copies the
+    blob to the device and sizes the workspace.  One staging buffer: planning the next batch first waits on the host for the
+    copy of the batch before it (not for its launches), as BoxDrawer does."""
+
+    def __init__(self, filter, device):
+        self.filter = check_filter(filter)
+        self.device = torch.device(device)
+        self._stage = None              # pinned host buffer the planner writes into
+        self._busy = None               # event recorded after the last copy out of it
+        self._ws = None                 # device workspace: the uint8 intermediates
+        self._keep = None               # what the launches in flight read
+
+    def _alloc(self, nbytes):
+        if self._stage is None or self._stage.numel() < nbytes:
+            t = torch.empty(max(2 * nbytes, 1 << 16), dtype=torch.uint8)
+            self._stage = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
+        return self._stage.data_ptr()
+
+    def plan(self, images, ow, oh):
+        """images: uint8 [h,w,3] tensors on self.device with pixel stride 3.  Returns (n, host address of the blob, its device
+        copy, blob bytes, workspace or None)."""
+        if self._busy is not None:
+            self._busy.synchronize()
+        descs = [(t.data_ptr(), max(t.stride(0), 3 * t.shape[1]), t.shape[0], t.shape[1]) for t in images]
+        nbytes, ws_bytes = ops.pil_resize_plan(descs, ow, oh, self.filter, self._alloc)
+        blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        blob.copy_(self._stage[:nbytes], non_blocking=True)
+        self._busy = torch.cuda.Event()
+        self._busy.record()
+        if ws_bytes and (self._ws is None or self._ws.numel() < ws_bytes):
+            self._ws = torch.empty(max(ws_bytes, 1 << 20), dtype=torch.uint8, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        for t in list(images) + ([self._ws] if ws_bytes else []):      # memory another stream's decoder or lane may own
+            t.record_stream(cur)
+        self._keep = (blob, list(images), self._ws)
+        return len(images), self._stage.data_ptr(), blob, nbytes, (self._ws if ws_bytes else None)
+
+
+def device_source(i, im, device):
+    """One source -> a uint8 [h,w,3] tensor on `device` the kernels read where it lies (pixel stride 3, channel stride 1, any row
+    pitch: a decoder output or a crop `big[3:3+h, 5:5+w]`); a numpy array is uploaded; anything else raises with the reason."""
+    if isinstance(im, np.ndarray):
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise PPYoloHipError('image %d: numpy %s %s, expected uint8 [h, w, 3]' % (i, im.dtype, tuple(im.shape)))
+        return torch.from_numpy(np.ascontiguousarray(im)).to(device, non_blocking=False)
+    if not isinstance(im, torch.Tensor):
+        raise PPYoloHipError('image %d: expected a uint8 [h, w, 3] device tensor or numpy array, got %s' % (i, type(im).__name__))
+    if im.dtype != torch.uint8:
+        raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
+    if im.dim() != 3 or im.shape[2] != 3:
+        raise PPYoloHipError('image %d: shape %s, expected [h, w, 3]' % (i, tuple(im.shape)))
+    if not _same_device(im.device, device):
+        raise PPYoloHipError('image %d lives on %s, the resizer on %s: upload it, or pass the numpy array' % (i, im.device, device))
+    h, w = im.shape[:2]
+    if h < 1 or w < 1:
+        raise PPYoloHipError('image %d: %d x %d, width and height must be in 1..65535' % (i, w, h))
+    if im.stride(1) != 3 or im.stride(2) != 1 or (h > 1 and im.stride(0) < 3 * w):
+        raise PPYoloHipError('image %d: strides %s: reading in place needs pixel stride 3, channel stride 1 and a row pitch of at '
+                             'least 3 * w' % (i, tuple(im.stride())))
+    return im
+
+
+class PilResizer(object):
+    """`Image.fromarray(im).resize(size, filter)` for a batch of 3-channel uint8 images of any sizes, on the device."""
+
+    def __init__(self, filter, device='cuda'):
+        self.device = torch.device(device)
+        self._planner = PilPlanner(filter, self.device)
+        self.filter = self._planner.filter
+
+    def __call__(self, images, size):
+        """images: list of uint8 [h,w,3] device tensors (read in place) or numpy arrays (uploaded); size = (ow, oh), Pillow's
+        order.  Returns a list of uint8 [oh, ow, 3] device tensors (views of one batch tensor), asynchronous on the current
+        stream: two launches, or one when no image changes its width."""
+        images = list(images)
+        if not images:
+            raise PPYoloHipError('empty batch')
+        try:
+            ow, oh = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise PPYoloHipError('size=%r: expected (width, height)' % (size,))
+        dev = [device_source(i, im, self.device) for i, im in enumerate(images)]
+        if ow < 1 or oh < 1:        # (the planner refuses the rest by name; an empty tensor cannot be allocated before it)
+            raise PPYoloHipError('output size %d x %d, each side must be in 1..8192' % (ow, oh))
+        n, h_blob, blob, nbytes, ws = self._planner.plan(dev, ow, oh)
+        out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device)
+        ops.pil_resize_u8(n, h_blob, blob, nbytes, ws, out)
+        return list(out.unbind(0))
+
+
+def parse_plan(blob):
+    """A planner blob (numpy uint8) -> dict(header fields, images = list of dicts, tables = {byte offset: dict(in, out, ksize,
+    kind, bounds int32 [out, 2], k int32 [out, ksize])}): the layout include/ppyolo_hip.h documents, for tests and tools."""
+    blob = np.ascontiguousarray(blob, dtype=np.uint8)
+    hi = blob[:32].view(np.int32)
+    hl = blob[32:48].view(np.int64)
+    ho = blob[48:56].view(np.int32)
+    hd = dict(magic=bytes(blob[:4]), n=int(hi[1]), ow=int(hi[2]), oh=int(hi[3]), filter=int(hi[4]), n_tables=int(hi[5]),
+              max_h_horizontal=int(hi[6]), mid_pitch=int(hi[7]), blob_bytes=int(hl[0]), ws_bytes=int(hl[1]),
+              desc_offset=int(ho[0]), table_offset=int(ho[1]), images=[], tables={})
+    for i in range(hd['n']):
+        rec = blob[hd['desc_offset'] + 48 * i:hd['desc_offset'] + 48 * (i + 1)]
+        q, d = rec.view(np.int64), rec.view(np.int32)
+        hd['images'].append(dict(base=int(q[0]), pitch=int(q[1]), h=int(d[4]), w=int(d[5]), xtab=int(d[6]), ytab=int(d[7]),
+                                 mid_offset=int(q[4])))
+    for im in hd['images']:
+        for off in (im['xtab'], im['ytab']):
+            if off < 0 or off in hd['tables']:
+                continue
+            t = blob[off:off + 16].view(np.int32)
+            insz, outsz, ksize, kind = (int(v) for v in t)
+            b0 = off + 16
+            bounds = blob[b0:b0 + 8 * outsz].view(np.int32).reshape(outsz, 2).copy()
+            k = blob[b0 + 8 * outsz:b0 + 8 * outsz + 4 * outsz * ksize].view(np.int32).reshape(outsz, ksize).copy()
+            hd['tables'][off] = dict(insz=insz, outsz=outsz, ksize=ksize, kind=kind, bounds=bounds, k=k)
+    return hd
+
+
+def plan_host(sizes, ow, oh, filter):
+    """The planner alone, without a device: sizes = list of (h, w) -> (numpy blob, workspace bytes).  The descriptors carry a
+    placeholder address; the blob is for inspection (parse_plan), not for a launch."""
+    hold = []
+
+    def alloc(nbytes):
+        hold.append(np.zeros((nbytes + 7) // 8, np.int64))
+        return hold[-1].ctypes.data
+
+    nbytes, ws_bytes = ops.pil_resize_plan([(8, 3 * w, h, w) for h, w in sizes], ow, oh, check_filter(filter), alloc)
+    return hold[-1].view(np.uint8)[:nbytes], ws_bytes
