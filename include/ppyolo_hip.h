@@ -607,7 +607,9 @@ int ppy_yolo_decode_levels_f32(int nlevels, const float *const *head_out, const 
  * out_dets [N][keep_top_k][6] = (label, score, x0,y0,x1,y1), rows >= out_count[n] are
  * -1; out_count[n] == 0 <=> the reference returns its [[-1]*6] sentinel.
  * out_keep_idx [N][keep_top_k] = box*C + class of every kept row (-1 padding).
- * Limits: 1 <= nms_top_k <= 1024, keep_top_k <= nms_top_k.
+ * Limits: 1 <= nms_top_k <= 1024, 1 <= keep_top_k <= nms_top_k (PPY_ERR_UNSUPPORTED outside, nothing is clamped).
+ * The first min(cand_count[n], cand_cap) entries of a list are used, in any order; a cand_cap that is not a multiple
+ * of 4 is accepted (tests/test_gpu_matrix_nms.py).
  * ws: ppy_matrix_nms_workspace_bytes(N) bytes of scratch, 16-byte aligned (the sorted top-k boxes and the
  * per-column compensate / decay values travel between the kernels of one call through it; round 4: + 264 KB per image
  * for the compact list of the large-list route).

@@ -1227,8 +1227,29 @@ def g23_norm_act():
     save('g23_norm_act_r50vd_96', **model_case('r50vd_96', PPYOLO_2x_Config, 96, 1, 'affine_channel', 'gn'))
 
 
+def g25_matrix_nms_cases():
+    """The reference's matrix_nms on every tie-free case of tests/matrix_nms_cases.py (the inputs are regenerated from the
+    builders, so only the configuration and the reference's rows are stored; tests/test_matrix_nms_cases.py holds the oracle to
+    them).  Tie cases have no reference answer: the oracle's documented total order is the contract there."""
+    for p in (ROOT, os.path.join(ROOT, 'tests')):
+        if p not in sys.path:
+            sys.path.append(p)            # behind the reference: its `config` / `model` keep their meaning
+    import matrix_nms_cases as mc
+    out, names = {}, mc.golden_names()
+    for name in names:
+        c = mc.get(name)
+        for n in range(c.N):
+            pred, cfg = _nms_case(c.boxes[n], c.scores[n], score_threshold=c.thr, post_threshold=c.post, nms_top_k=c.top_k,
+                                  keep_top_k=c.keep_k, use_gaussian=c.gauss, gaussian_sigma=c.sigma)
+            out['%s.%d' % (name, n)] = pred
+        out[name + '.cfg'] = np.array(c.cfg + (c.N, c.M, c.C, c.meta.get('seed', -1)), dtype=np.float64)
+        print('   %-28s %s rows' % (name, [int(out['%s.%d' % (name, n)].shape[0]) for n in range(c.N)]))
+    out['names'] = np.array(names)
+    save('g25_matrix_nms_cases', **out)
+
+
 ALL = dict(g1=g1_conv_units, g2=g2_dcn, g3=g3_coord_spp, g4=g4_decode, g5=g5_matrix_nms, g67=g6_g7_models,
-           g8=g8_preprocess, g9=g9_decode_harness, g10=g10_coco_records, g11=g11_state_dict_layout, g12=g12_train_step, g13=g13_ema, g14=g14_train_loop, g15=g15_dcn_backward, g16=g16_train_step_backbone, g17=g17_paddle_names, g18=g18_headline_sizes, g19=g19_augment, g23=g23_norm_act)
+           g8=g8_preprocess, g9=g9_decode_harness, g10=g10_coco_records, g11=g11_state_dict_layout, g12=g12_train_step, g13=g13_ema, g14=g14_train_loop, g15=g15_dcn_backward, g16=g16_train_step_backbone, g17=g17_paddle_names, g18=g18_headline_sizes, g19=g19_augment, g23=g23_norm_act, g25=g25_matrix_nms_cases)
 
 if __name__ == '__main__':
     ap = argparse.ArgumentParser()
