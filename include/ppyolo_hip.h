@@ -1016,6 +1016,45 @@ int ppy_affine_bwd_f32(const float *x, int x_ld, const float *weight, const floa
 int ppy_mish_bwd_f32(const float *x, int x_ld, const float *scale, const float *shift, const float *dy, int dy_ld, float *dx, int dx_ld,
                      int N, int H, int W, int C, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * PNG reconstruction: inflated scanline streams -> the uint8 HWC BGR device images cv2.imread(path) gives for a PNG file
+ * (reference demo.py:41, tools/cocotools.py:105, tools/transform.py:87; pinned to Pillow / libpng).
+ * The library links no zlib: the caller walks the chunks (signature, CRCs, IHDR, PLTE), inflates the concatenated IDAT data
+ * and hands in, per image, the SCANLINE STREAM -- for the single image or for each non-empty Adam7 pass in turn, rows of
+ * 1 filter-type byte + ceil(cols * channels * depth / 8) bytes -- and a descriptor.  ppyolo_hip/png.py is that caller in Python.
+ *
+ * Accepted: colour types 0, 2, 3, 4, 6 at every bit depth the PNG specification pairs them with; interlace 0 or 1.  Grey is
+ * replicated to B = G = R (depth 1 / 2 / 4 scaled by 255 / 85 / 17), a palette index is looked up in `palette` (an index at or
+ * past palette_entries gives black), an alpha channel is dropped, a 16-bit sample gives its high byte.
+ *
+ * A batch: place the streams in one buffer at offsets that are multiples of 16 (desc.scan_offset), each followed by padding up
+ * to the next multiple of 16; ppy_png_pack_table writes the device descriptor table (ppy_png_table_bytes(n) bytes, palettes
+ * included) for the output pointers into host memory; copy table and streams to the device (one copy when they share a pinned
+ * buffer); ppy_png_reconstruct_u8 enqueues ONE launch for the whole batch, one workgroup per (image, Adam7 pass), and never
+ * synchronises.  out[i]: device uint8 [height][row_stride[i] bytes], pixel (y, x) channel c at y * row_stride + 3 * x + c,
+ * row_stride >= 3 * width, any alignment.  ws: ppy_png_workspace_bytes(n, descs) bytes (0 = a descriptor is invalid), 16-byte
+ * aligned (the last row of each band of 1024 rows is handed to the next band through it); table and scan 16-byte aligned.
+ * A filter-type byte above 4 is the caller's to refuse; the kernel reads such a row as filter 0.
+ * TRUST BOUNDARY as for ppy_jpeg_reconstruct_u8: h_descs are validated on the host (geometry, scan_bytes against the
+ * expected length, stream ranges against the buffer, workspace size) and size the launch; the kernel reads the device table,
+ * output pointers and row strides included, WITHOUT further checks.  The table must be the one ppy_png_pack_table wrote from
+ * these very descriptors, unmodified. */
+typedef struct ppy_png_desc_t {
+    int width, height;                /* 1..65535 */
+    int bit_depth, colour_type;       /* as in IHDR */
+    int interlace;                    /* 0, or 1 = Adam7 */
+    int palette_entries;              /* 0..256; colour type 3 needs at least 1 */
+    long long scan_offset;            /* CALLER: byte offset of the image's stream in the scan buffer, % 16 == 0 */
+    long long scan_bytes;             /* its length: the sum over non-empty passes of rows * (1 + row bytes), exactly */
+    unsigned char palette[768];       /* PLTE: R, G, B per entry */
+} ppy_png_desc_t;
+size_t ppy_png_table_bytes(int n);
+int ppy_png_pack_table(int n, const ppy_png_desc_t *h_descs, unsigned char *const *h_out, const long long *h_row_stride, void *h_table,
+                       size_t table_bytes);
+size_t ppy_png_workspace_bytes(int n, const ppy_png_desc_t *h_descs);
+int ppy_png_reconstruct_u8(int n, const ppy_png_desc_t *h_descs, const void *table, const void *scan, size_t scan_bytes, void *ws,
+                           size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

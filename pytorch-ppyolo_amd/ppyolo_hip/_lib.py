@@ -82,6 +82,12 @@ class JpegEncSizes(ctypes.Structure):
     _fields_ = [('table_bytes', c_size_t), ('coef_bytes', c_size_t), ('ws_bytes', c_size_t), ('out_bytes', c_size_t)]
 
 
+class PngDesc(ctypes.Structure):
+    """ppy_png_desc_t (include/ppyolo_hip.h)."""
+    _fields_ = [('width', c_int), ('height', c_int), ('bit_depth', c_int), ('colour_type', c_int), ('interlace', c_int),
+                ('palette_entries', c_int), ('scan_offset', c_longlong), ('scan_bytes', c_longlong), ('palette', ctypes.c_ubyte * 768)]
+
+
 class DrawImage(ctypes.Structure):
     """ppy_draw_image_t (include/ppyolo_hip.h)."""
     _fields_ = [('base', c_void_p), ('pitch', c_longlong), ('h', c_int), ('w', c_int)]
@@ -246,6 +252,10 @@ _PROTOS = {
     'ppy_jpeg_enc_scan_device': (c_int, [c_int, ctypes.POINTER(JpegEncDesc), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                          c_void_p, c_size_t, c_void_p]),
     'ppy_jpeg_enc_scan_host': (c_int, [ctypes.POINTER(JpegEncDesc), c_void_p, c_size_t, c_void_p, c_size_t, ctypes.POINTER(c_size_t), c_void_p]),
+    'ppy_png_table_bytes': (c_size_t, [c_int]),
+    'ppy_png_pack_table': (c_int, [c_int, ctypes.POINTER(PngDesc), ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_void_p, c_size_t]),
+    'ppy_png_workspace_bytes': (c_size_t, [c_int, ctypes.POINTER(PngDesc)]),
+    'ppy_png_reconstruct_u8': (c_int, [c_int, ctypes.POINTER(PngDesc), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
     'ppy_draw_detections_u8': (c_int, [c_int, ctypes.POINTER(DrawImage), c_void_p, c_void_p, c_void_p, c_int, c_float, c_void_p, c_int,
                                        c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p, c_void_p]),
     'ppy_group_norm_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_void_p, c_int, c_int]
