@@ -32,6 +32,7 @@ import torch
 
 from . import ops, targets
 from ._lib import PPYoloHipError
+from .hostio import check_image
 from .preprocess import normalisation_table
 
 NEAREST, LINEAR, CUBIC, AREA, LANCZOS4 = 0, 1, 2, 3, 4        # cv2.INTER_* codes
@@ -556,27 +557,13 @@ class TrainBatchBuilder(object):
         return self(decode_records(records, decoder, fallback, with_mixup=self.with_mixup), shape, rng)
 
 
-def _same_device(a, b):
-    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
-
-
 def source_image(im, device):
     """What the builder makes of a record's image: a numpy uint8 [h,w,3] array (as given, or the one a CPU tensor wraps) is a
-    HOST source, packed into the blob; a uint8 [h,w,3] tensor on `device` with x-stride 3 and channel stride 1 is returned as
-    it is, an EXTERNAL source the kernels read in place.  Anything else raises: nothing is copied silently."""
+    HOST source, packed into the blob; a uint8 [h,w,3] tensor on `device` under hostio.check_image's rule is returned as it
+    is, an EXTERNAL source the kernels read in place.  Anything else raises: nothing is copied silently."""
     if isinstance(im, torch.Tensor):
-        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
-            raise PPYoloHipError('expected a decoded uint8 image [h, w, 3], got %s %s' % (im.dtype, tuple(im.shape)))
-        if im.device.type == 'cpu':
-            return im.numpy()
-        if not _same_device(im.device, torch.device(device)):
-            raise PPYoloHipError('image tensor lives on %s, the builder on %s: move it there (`.to(device)`) or pass a numpy '
-                                 'array' % (im.device, device))
-        if im.stride(2) != 1 or im.stride(1) != 3 or (im.shape[0] > 1 and im.stride(0) < 3 * im.shape[1]):
-            raise PPYoloHipError('image tensor with strides %s: a device source needs channel stride 1, x-stride 3 and rows '
-                                 'that do not overlap (HWC; any row pitch); call `.contiguous()` on it first'
-                                 % (tuple(im.stride()),))
-        return im
+        check_image(None, im, device, 'source', host=True)
+        return im.numpy() if im.device.type == 'cpu' else im
     if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
         raise PPYoloHipError('expected a decoded uint8 image [h, w, 3]')
     return im

@@ -14,10 +14,7 @@ import torch
 
 from . import _lib, label_font, ops
 from ._lib import PPYoloHipError
-
-
-def _same_device(a, b):
-    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
+from .hostio import Staging, check_image, row_pitch, same_device
 
 
 def class_colors(num_classes):
@@ -49,8 +46,7 @@ class BoxDrawer(object):
         self.colors = class_colors(self.num_classes)
         self._h_name_len = (ctypes.c_int * self.num_classes)(*[len(n) for n in self.all_classes])
         self._tables = None             # (colors, names, name_len, font) on the device
-        self._stage = None              # pinned buffer the image table is written into
-        self._busy = None               # event recorded after the last copy out of it
+        self._staging = Staging(self.device, 1 << 12)       # the image table is written into it
 
     # ---- the parts --------------------------------------------------------------------------------------------------------
     def _upload(self):
@@ -65,32 +61,18 @@ class BoxDrawer(object):
         return self._tables
 
     def _target(self, i, im):
-        """One image -> itself, if the kernel can draw on it where it lies: a uint8 tensor [h,w,3] on the drawer's device with
-        pixel stride 3 and channel stride 1, any row pitch (JpegEncoder._source's device rule).  Host memory is refused, not
-        uploaded: the caller would never see the drawing (draw_host is the call for a numpy image)."""
+        """One image -> itself, if the kernel can draw on it where it lies (hostio.check_image, sides in 1..65535).  Host memory
+        is refused, not uploaded: the caller would never see the drawing (draw_host is the call for a numpy image)."""
         if not isinstance(im, torch.Tensor):
             raise PPYoloHipError('image %d: expected a uint8 device tensor [h, w, 3], got %s: BoxDrawer draws in place and does not '
                                  'copy a host array (draw_host takes a numpy image)' % (i, type(im).__name__))
-        if im.dtype != torch.uint8:
-            raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
-        if im.dim() != 3 or im.shape[2] != 3:
-            raise PPYoloHipError('image %d: shape %s, expected [h, w, 3]' % (i, tuple(im.shape)))
-        h, w = im.shape[:2]
-        if not (1 <= h <= 65535 and 1 <= w <= 65535):
-            raise PPYoloHipError('image %d: %d x %d, width and height must be in 1..65535' % (i, w, h))
-        if im.stride(1) != 3 or im.stride(2) != 1 or (h > 1 and im.stride(0) < 3 * w):
-            raise PPYoloHipError('image %d: strides %s: drawing in place needs pixel stride 3, channel stride 1 and rows that do '
-                                 'not overlap (any row pitch)' % (i, tuple(im.stride())))
-        if not _same_device(im.device, self.device):
-            raise PPYoloHipError('image %d lives on %s, the drawer on %s: BoxDrawer draws in place and does not copy'
-                                 % (i, im.device, self.device))
-        return im
+        return check_image(i, im, self.device, 'drawing in place', bound=True)
 
     def _rows(self, n, dets, count):
         for name, t, dtype in (('dets', dets, torch.float32), ('count', count, torch.int32)):
             if not isinstance(t, torch.Tensor):
                 raise PPYoloHipError('%s: expected a device tensor as forward_padded returns it, got %s' % (name, type(t).__name__))
-            if not _same_device(t.device, self.device):
+            if not same_device(t.device, self.device):
                 raise PPYoloHipError('%s lives on %s, the drawer on %s' % (name, t.device, self.device))
             if t.dtype != dtype:
                 raise PPYoloHipError('%s: dtype %s, expected %s' % (name, t.dtype, dtype))
@@ -108,8 +90,8 @@ class BoxDrawer(object):
         current stream, nothing read back.  images: list of uint8 [h,w,3] device tensors (decoder outputs, crops of larger
         tensors, ...); dets [N,K,6] float32 and count [N] int32 as PPYOLO.forward_padded returns them.  Returns `images`.
         The image table crosses in one small copy out of ONE pinned staging buffer, so a second call first waits on the host
-        for the copy of the call before it (not for its launch), as JpegEncoder.coefficients does: calls queued back to back
-        behind a deep stream are paced by that copy."""
+        for the copy of the call before it (not for its launch; hostio.Staging): calls queued back to back behind a deep stream
+        are paced by that copy."""
         images = list(images)
         n = len(images)
         if n == 0:
@@ -120,17 +102,10 @@ class BoxDrawer(object):
         colors, names, name_len, font = self._upload()
         descs = (_lib.DrawImage * n)()
         for d, t in zip(descs, images):
-            d.base, d.pitch, d.h, d.w = t.data_ptr(), max(t.stride(0), 3 * t.shape[1]), t.shape[0], t.shape[1]
+            d.base, d.pitch, d.h, d.w = t.data_ptr(), row_pitch(t), t.shape[0], t.shape[1]
         nbytes = ctypes.sizeof(descs)
-        if self._busy is not None:              # the last copy out of the staging buffer
-            self._busy.synchronize()
-        if self._stage is None or self._stage.numel() < nbytes:
-            self._stage = torch.empty(max(nbytes, 1 << 12), dtype=torch.uint8).pin_memory()
-        ctypes.memmove(self._stage.data_ptr(), descs, nbytes)
-        table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        table.copy_(self._stage[:nbytes], non_blocking=True)
-        self._busy = torch.cuda.Event()
-        self._busy.record()
+        ctypes.memmove(self._staging.acquire(nbytes).data_ptr(), descs, nbytes)
+        table = self._staging.upload(nbytes)
         cur = torch.cuda.current_stream(self.device)
         for t in images + [dets, count]:        # the launch touches memory another stream's decoder or lane may own
             t.record_stream(cur)

@@ -5,7 +5,7 @@ the `decoder=` hook of Decode.detect_files / annotate_files, TrainBatchBuilder.f
 import re
 
 from ._lib import PPYoloHipError
-from .jpeg import _bytes
+from .hostio import ImreadMixin, read_bytes
 
 PNG_SIGNATURE = b'\x89PNG\r\n\x1a\n'
 
@@ -24,7 +24,7 @@ def _neither(data):
     return 'neither a JPEG nor a PNG file (first bytes %s)' % (bytes(data[:8]).hex() or 'missing')
 
 
-class ImageDecoder(object):
+class ImageDecoder(ImreadMixin):
     def __init__(self, jpeg=None, png=None):
         """jpeg / png: the caller's decoders (any object with decode and, optionally, refusal); default: a JpegDecoder() and a
         PngDecoder() of this object's own, made when the first file of the kind arrives."""
@@ -42,7 +42,7 @@ class ImageDecoder(object):
 
     def refusal(self, item):
         """None, or (kind, reason) as the item's own decoder gives it; an item of neither format is 'unsupported'."""
-        data = _bytes(item)
+        data = read_bytes(item)
         kind = sniff(data)
         if kind is None:
             return 'unsupported', _neither(data)
@@ -52,7 +52,7 @@ class ImageDecoder(object):
     def decode(self, items, out=None):
         """list of bytes / memoryview / paths of either format -> list of uint8 [h,w,3] BGR device tensors in the caller's
         order.  `item i:` in an error is the caller's index."""
-        datas = [_bytes(it) for it in items]
+        datas = [read_bytes(it) for it in items]
         if not datas:
             raise PPYoloHipError('empty batch')
         if out is not None and len(out) != len(datas):
@@ -81,9 +81,3 @@ class ImageDecoder(object):
             for i, im in zip(idx, ims):
                 result[i] = im
         return result
-
-    def imdecode(self, buf):
-        return self.decode([buf])[0]
-
-    def imread(self, path):
-        return self.decode([path])[0]

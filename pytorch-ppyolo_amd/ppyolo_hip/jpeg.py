@@ -24,26 +24,15 @@ JpegEncoder is the same codec run the other way: uint8 device images -> the byte
 (csrc/jpeg_encode.hip): pixels -> the coefficient buffer the decoder defines -> entropy-coded bytes; the host writes the
 headers and reads lengths and bytes back (two copies, one stream wait per call)."""
 import ctypes
-import os
-import threading
-from concurrent.futures import ThreadPoolExecutor
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import PPYoloHipError, lib
 from ._lib import check as _check
-
-MAX_THREADS = 16
-
-
-def _bytes(item):
-    if isinstance(item, (bytes, bytearray, memoryview)):
-        return bytes(item)
-    if isinstance(item, (str, os.PathLike)):
-        with open(item, 'rb') as fh:
-            return fh.read()
-    raise PPYoloHipError('expected bytes, a memoryview or a path, got %s' % type(item).__name__)
+from .hostio import MAX_THREADS      # noqa: F401 (re-exported)
+from .hostio import HostPool, ImreadMixin, Staging, StagingRing, check_image, check_outputs, read_bytes, row_pitch
 
 
 def _refuse(i, rc, reason):
@@ -69,7 +58,7 @@ class HostBatch(object):
                  'scan_bytes', 'coef_bytes', 'status')
 
 
-class JpegDecoder(object):
+class JpegDecoder(ImreadMixin):
     def __init__(self, device='cuda', threads=None, apply_orientation=True, max_pixels=1 << 28, entropy='host', subseq_bytes=None,
                  accept='baseline'):
         """entropy: 'host' (Huffman decoding on the thread pool) or 'device' (on the GPU; the pool runs the marker pass alone).
@@ -93,56 +82,26 @@ class JpegDecoder(object):
             raise PPYoloHipError('subseq_bytes must be a power of two in [%d, %d]' % (_lib.JPEG_SUBSEQ_MIN, _lib.JPEG_SUBSEQ_MAX))
         self.last_status = None         # device mode: the status tensor of the last reconstruct()
         self.device = torch.device(device)
-        if threads is not None and threads < 1:
-            raise PPYoloHipError('threads must be >= 1')
-        self.threads = None if threads is None else min(int(threads), MAX_THREADS)
+        self._host = HostPool(threads, 'ppy-jpeg')
+        self.threads = self._host.threads
         self.apply_orientation = bool(apply_orientation)
-        self._pool = None
-        self._stage = [None, None]      # pinned uint8 buffers, used in turn
-        self._busy = [None, None]       # event recorded after the copy out of each
-        self._held = [False, False]     # handed out in a HostBatch that has not been reconstructed or released yet
-        self._gen = [0, 0]              # how many batches each buffer has been handed to
-        self._turn = 0
-        self._lock = threading.Lock()   # entropy_decode and reconstruct may run on two threads
+        self._ring = StagingRing(self.device, 1 << 20, stage='entropy')     # entropy_decode and reconstruct may run on two threads
 
     # ---- host stage ---------------------------------------------------------------------------------------------------
+    _pool = property(lambda self: self._host.executor)      # None until a call needs more than one worker
+
     def _staging(self, nbytes):
-        with self._lock:
-            s = self._turn if not self._held[self._turn] else self._turn ^ 1
-            if self._held[s]:
-                raise PPYoloHipError('both staging buffers belong to batches that wait for reconstruct(): the entropy stage may '
-                                     'run at most two batches ahead; reconstruct() or release() one first')
-            self._held[s] = True
-            self._gen[s] += 1
-            gen = self._gen[s]
-            self._turn = s ^ 1
-            busy, self._busy[s] = self._busy[s], None
-        if busy is not None:                    # the last copy out of this buffer
-            busy.synchronize()
-        if self._stage[s] is None or self._stage[s].numel() < nbytes:
-            t = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8)
-            self._stage[s] = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
-        return s, gen, self._stage[s]
+        return self._ring.take(nbytes)
 
     def release(self, hb):
         """Give back the staging buffer of a HostBatch that will not be reconstructed."""
-        with self._lock:
-            if self._gen[hb.slot] == hb.gen:
-                self._held[hb.slot] = False
-
-    def _map(self, fn, n):
-        workers = min(self.threads or MAX_THREADS, n)
-        if workers <= 1:
-            return [fn(i) for i in range(n)]
-        if self._pool is None:
-            self._pool = ThreadPoolExecutor(max_workers=self.threads or MAX_THREADS, thread_name_prefix='ppy-jpeg')
-        return list(self._pool.map(fn, range(n)))
+        self._ring.release(hb.slot, hb.gen)
 
     def refusal(self, item):
         """Header pass only, nothing is decoded: None if decode() would take the item as far as its markers tell, otherwise
         (kind, reason) with kind 'unsupported' (progressive, arithmetic, ...: a file for another decoder) or 'corrupt'.
         Damage inside the entropy data still surfaces in decode()."""
-        data = _bytes(item)
+        data = read_bytes(item)
         info = _lib.JpegInfo()
         rc = lib().ppy_jpeg_info_ex(data, len(data), self.accept, ctypes.byref(info))
         if rc == _lib.OK:
@@ -154,7 +113,7 @@ class JpegDecoder(object):
         until reconstruct(hb) or release(hb); there are two buffers, so at most two batches can wait at a time (a third call
         raises instead of overwriting one).  May run on another thread than reconstruct()."""
         L = lib()
-        datas = [_bytes(it) for it in items]
+        datas = [read_bytes(it) for it in items]
         n = len(datas)
         if n == 0:
             raise PPYoloHipError('empty batch')
@@ -187,7 +146,7 @@ class JpegDecoder(object):
             return rc, reason.value
 
         try:
-            for i, (rc, reason) in enumerate(self._map(one, n)):
+            for i, (rc, reason) in enumerate(self._host.map(one, n)):
                 if rc != _lib.OK:
                     raise _refuse(i, rc, reason)
         except BaseException:
@@ -210,7 +169,7 @@ class JpegDecoder(object):
             bound = L.ppy_jpeg_scan_bytes(datas[i], len(datas[i]), ctypes.byref(segs)) if rc == _lib.OK else 0
             return rc, info, bound, segs
 
-        for i, (rc, info, bound, segs) in enumerate(self._map(size, n)):
+        for i, (rc, info, bound, segs) in enumerate(self._host.map(size, n)):
             d = datas[i]
             if rc != _lib.OK:
                 raise _refuse(i, rc, info.reason)
@@ -240,7 +199,7 @@ class JpegDecoder(object):
             return rc, reason.value
 
         try:
-            for i, (rc, reason) in enumerate(self._map(one, n)):
+            for i, (rc, reason) in enumerate(self._host.map(one, n)):
                 if rc != _lib.OK:
                     raise _refuse(i, rc, reason)
         except BaseException:
@@ -263,47 +222,31 @@ class JpegDecoder(object):
         shapes = [(s[2], s[3]) if ori else (s[0], s[1]) for s in hb.sizes]
         if out is None:
             out = [torch.empty((h, w, 3), dtype=torch.uint8, device=self.device) for h, w in shapes]
-        if len(out) != n:
-            raise PPYoloHipError('%d output tensors for %d images' % (len(out), n))
-        for t, (h, w) in zip(out, shapes):
-            if not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w, 3) or t.stride(2) != 1 or t.stride(1) != 3 \
-                    or (h > 1 and t.stride(0) < 3 * w):
-                raise PPYoloHipError('output must be a uint8 device tensor [%d, %d, 3] with pixel stride 3' % (h, w))
-        with self._lock:
-            if self._gen[hb.slot] != hb.gen:
-                raise PPYoloHipError('stale HostBatch: its staging buffer has been handed to a later batch')
-            self._held[hb.slot] = True          # (again, when the same batch is reconstructed a second time)
-            busy = self._busy[hb.slot]
-        if busy is not None:                    # the same HostBatch again: its last copy still reads the table
-            busy.synchronize()
-        _check(L.ppy_jpeg_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
-                                     (ctypes.c_longlong * n)(*[max(t.stride(0), 3 * t.shape[1]) for t in out]), int(ori),
-                                     hb.stage.data_ptr(), hb.table_bytes), 'ppy_jpeg_pack_table')
-        device_entropy = hb.entropy == 'device'
-        if device_entropy:
-            h_plan = hb.stage.data_ptr() + hb.table_bytes
-            ent_ws = ctypes.c_size_t()
-            _check(L.ppy_jpeg_entropy_plan(n, hb.descs, h_plan + hb.plan_bytes, hb.scan_bytes, (ctypes.c_longlong * n)(*hb.scan_off),
-                                           self.subseq_bytes, h_plan, hb.plan_bytes, ctypes.byref(ent_ws)), 'ppy_jpeg_entropy_plan')
-        blob = torch.empty(hb.total_bytes, dtype=torch.uint8, device=self.device)
-        blob.copy_(hb.stage[:hb.total_bytes], non_blocking=True)
-        stream = torch.cuda.current_stream().cuda_stream
-        if device_entropy:      # enqueued before the staging buffer is given back: the call sizes its grids from the host plan
-            coef = torch.empty(max(hb.coef_bytes, 16), dtype=torch.uint8, device=self.device)
-            coef_ptr, coef_bytes = coef.data_ptr(), hb.coef_bytes
-            status = torch.empty((3, n), dtype=torch.int32, device=self.device)
-            ent = torch.empty(max(ent_ws.value, 16), dtype=torch.uint8, device=self.device)
-            _check(L.ppy_jpeg_entropy_device(n, h_plan, blob.data_ptr() + hb.table_bytes, blob.data_ptr() + hb.table_bytes + hb.plan_bytes,
-                                             self.subseq_bytes, coef_ptr, coef_bytes, status.data_ptr(), ent.data_ptr(), ent_ws.value, stream),
-                   'ppy_jpeg_entropy_device')
-            hb.status = self.last_status = status
         else:
-            coef_ptr, coef_bytes = blob.data_ptr() + hb.table_bytes, hb.total_bytes - hb.table_bytes
-        ev = torch.cuda.Event()
-        ev.record()
-        with self._lock:
-            self._busy[hb.slot] = ev
-            self._held[hb.slot] = False
+            check_outputs(out, shapes, self.device)
+        device_entropy = hb.entropy == 'device'
+        with self._ring.uploading(hb.slot, hb.gen) as staging:
+            _check(L.ppy_jpeg_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
+                                         (ctypes.c_longlong * n)(*[row_pitch(t) for t in out]), int(ori),
+                                         hb.stage.data_ptr(), hb.table_bytes), 'ppy_jpeg_pack_table')
+            if device_entropy:
+                h_plan = hb.stage.data_ptr() + hb.table_bytes
+                ent_ws = ctypes.c_size_t()
+                _check(L.ppy_jpeg_entropy_plan(n, hb.descs, h_plan + hb.plan_bytes, hb.scan_bytes, (ctypes.c_longlong * n)(*hb.scan_off),
+                                               self.subseq_bytes, h_plan, hb.plan_bytes, ctypes.byref(ent_ws)), 'ppy_jpeg_entropy_plan')
+            blob = staging.copy(hb.total_bytes)
+            stream = torch.cuda.current_stream().cuda_stream
+            if device_entropy:      # enqueued before the staging buffer is given back: the call sizes its grids from the host plan
+                coef = torch.empty(max(hb.coef_bytes, 16), dtype=torch.uint8, device=self.device)
+                coef_ptr, coef_bytes = coef.data_ptr(), hb.coef_bytes
+                status = torch.empty((3, n), dtype=torch.int32, device=self.device)
+                ent = torch.empty(max(ent_ws.value, 16), dtype=torch.uint8, device=self.device)
+                _check(L.ppy_jpeg_entropy_device(n, h_plan, blob.data_ptr() + hb.table_bytes, blob.data_ptr() + hb.table_bytes + hb.plan_bytes,
+                                                 self.subseq_bytes, coef_ptr, coef_bytes, status.data_ptr(), ent.data_ptr(), ent_ws.value, stream),
+                       'ppy_jpeg_entropy_device')
+                hb.status = self.last_status = status
+            else:
+                coef_ptr, coef_bytes = blob.data_ptr() + hb.table_bytes, hb.total_bytes - hb.table_bytes
         ws_bytes = L.ppy_jpeg_workspace_bytes(n, hb.descs)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
         _check(L.ppy_jpeg_reconstruct_u8(n, hb.descs, int(ori), blob.data_ptr(), coef_ptr, coef_bytes, ws.data_ptr(), ws_bytes, stream),
@@ -319,22 +262,16 @@ class JpegDecoder(object):
     def decode(self, items, out=None, check=True):
         """list of bytes / memoryview / paths -> list of uint8 [h,w,3] BGR device tensors, asynchronous on the current stream
         (the device entropy mode with check=True waits for its status words: reconstruct())."""
-        return self.reconstruct(self.entropy_decode(items), out=out, check=check)
-
-    def imdecode(self, buf):
-        return self.decode([buf])[0]
-
-    def imread(self, path):
-        return self.decode([path])[0]
+        hb = self.entropy_decode(items)
+        try:
+            return self.reconstruct(hb, out=out, check=check)
+        except BaseException:
+            self.release(hb)        # (outputs refused: the batch never reached the device; after the copy this changes nothing)
+            raise
 
 
 # ---- encoding ---------------------------------------------------------------------------------------------------------------
 SUBSAMPLINGS = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
-
-
-def _same_device(a, b):
-    return a.type == b.type and (a.index if a.index is not None else torch.cuda.current_device()) == \
-        (b.index if b.index is not None else torch.cuda.current_device())
 
 
 class EncBatch(object):
@@ -368,8 +305,7 @@ class JpegEncoder(object):
         self.device = torch.device(device)
         h, v = SUBSAMPLINGS[subsampling]
         self.params = _lib.JpegEncParams(quality, h, v, restart_interval)
-        self._stage = None              # pinned buffer the descriptor table is packed into
-        self._busy = None               # event recorded after the last copy out of it
+        self._staging = Staging(self.device, 1 << 16)       # the descriptor table is packed into it
 
     # ---- the parts --------------------------------------------------------------------------------------------------------
     def quant_tables(self):
@@ -389,33 +325,14 @@ class JpegEncoder(object):
         return buf.raw[:used.value]
 
     def _source(self, i, im):
-        """One input -> a device tensor the kernels read in place (augment.source_image's rule): a uint8 tensor on the
-        encoder's device, [h,w,3] with pixel stride 3 and channel stride 1 or [h,w] with pixel stride 1, any row pitch;
-        numpy arrays and CPU tensors of those shapes are uploaded.  Anything else raises: nothing is copied silently."""
-        if not isinstance(im, torch.Tensor):
-            import numpy as np
-            if not isinstance(im, np.ndarray):
-                raise PPYoloHipError('image %d: expected a uint8 tensor or numpy array [h, w, 3] or [h, w], got %s' % (i, type(im).__name__))
+        """One input -> a device tensor the kernels read in place (hostio.check_image, [h,w] grey included, sides in 1..65535);
+        numpy arrays and CPU tensors of those shapes are uploaded."""
+        if isinstance(im, np.ndarray):
             if im.dtype != np.uint8:
                 raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
             im = torch.from_numpy(np.ascontiguousarray(im))
-        if im.dtype != torch.uint8:
-            raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
-        if im.dim() not in (2, 3) or (im.dim() == 3 and im.shape[2] != 3):
-            raise PPYoloHipError('image %d: shape %s, expected [h, w, 3] (BGR) or [h, w] (grey)' % (i, tuple(im.shape)))
-        h, w = im.shape[:2]
-        if not (1 <= h <= 65535 and 1 <= w <= 65535):
-            raise PPYoloHipError('image %d: %d x %d, width and height must be in 1..65535' % (i, w, h))
-        if im.device.type == 'cpu':
-            return im.contiguous().to(self.device, non_blocking=False)
-        if not _same_device(im.device, self.device):
-            raise PPYoloHipError('image %d lives on %s, the encoder on %s: move it there (`.to(device)`) or pass a numpy array'
-                                 % (i, im.device, self.device))
-        pix = 3 if im.dim() == 3 else 1
-        if im.stride(1) != pix or (pix == 3 and im.stride(2) != 1) or (h > 1 and im.stride(0) < pix * w):
-            raise PPYoloHipError('image %d: strides %s: a source needs pixel stride %d%s and rows that do not overlap (any row '
-                                 'pitch); call `.contiguous()` on it first' % (i, tuple(im.stride()), pix, ', channel stride 1' if pix == 3 else ''))
-        return im
+        check_image(i, im, self.device, 'source', grey=True, bound=True, host=True)
+        return im.contiguous().to(self.device, non_blocking=False) if im.device.type == 'cpu' else im
 
     def coefficients(self, images):
         """Stage 1: colour conversion, padding, downsampling, forward DCT and quantisation of the whole batch in one launch on
@@ -434,18 +351,11 @@ class JpegEncoder(object):
         rc = L.ppy_jpeg_enc_layout(ctypes.byref(self.params), n, descs, ctypes.byref(sizes), reason)
         if rc != _lib.OK:
             raise PPYoloHipError('cannot encode: %s (code %d)' % (reason.value.decode() or L.ppy_error_string(rc).decode(), rc))
-        if self._busy is not None:              # the last copy out of the staging buffer
-            self._busy.synchronize()
-        if self._stage is None or self._stage.numel() < sizes.table_bytes:
-            t = torch.empty(max(sizes.table_bytes, 1 << 16), dtype=torch.uint8)
-            self._stage = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
-        _check(L.ppy_jpeg_enc_pack_table(ctypes.byref(self.params), n, descs, self._stage.data_ptr(), sizes.table_bytes), 'ppy_jpeg_enc_pack_table')
+        stage = self._staging.acquire(sizes.table_bytes)
+        _check(L.ppy_jpeg_enc_pack_table(ctypes.byref(self.params), n, descs, stage.data_ptr(), sizes.table_bytes), 'ppy_jpeg_enc_pack_table')
         eb = EncBatch()
         eb.n, eb.descs, eb.sizes, eb.sources = n, descs, sizes, srcs
-        eb.table = torch.empty(sizes.table_bytes, dtype=torch.uint8, device=self.device)
-        eb.table.copy_(self._stage[:sizes.table_bytes], non_blocking=True)
-        self._busy = torch.cuda.Event()
-        self._busy.record()
+        eb.table = self._staging.upload(sizes.table_bytes)
         eb.coef = torch.empty(max(sizes.coef_bytes, 16), dtype=torch.uint8, device=self.device)
         _check(L.ppy_jpeg_enc_coefficients(n, descs, eb.table.data_ptr(), eb.coef.data_ptr(), sizes.coef_bytes,
                                            torch.cuda.current_stream().cuda_stream), 'ppy_jpeg_enc_coefficients')

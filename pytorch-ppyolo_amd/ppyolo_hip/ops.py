@@ -13,6 +13,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .hostio import row_pitch
 from ._lib import ACT, CFG_FAMILIES, CFG_OPERANDS, CFG_SPLITK, ConvCfg, check, conv_cfg, conv_cfgs, lib      # noqa: F401 (the descriptors: host queries)
 
 
@@ -584,7 +585,7 @@ def _augment_sources(blob, sources):
         assert im.stride(2) == 1 and im.stride(1) == 3 and im.device == blob.device
         assert im.shape[0] > 0 and im.shape[1] > 0 and (im.shape[0] == 1 or im.stride(0) >= 3 * im.shape[1])
     return (n, (ctypes.c_void_p * n)(*[im.data_ptr() for im in sources]),
-            (ctypes.c_longlong * n)(*[max(im.stride(0), 3 * im.shape[1]) for im in sources]),
+            (ctypes.c_longlong * n)(*[row_pitch(im) for im in sources]),
             (ctypes.c_int * n)(*[im.shape[0] for im in sources]), (ctypes.c_int * n)(*[im.shape[1] for im in sources]))
 
 

@@ -17,11 +17,8 @@ A file outside the subset raises PPYoloHipError('item i: unsupported PNG: <reaso
 <reason>'."""
 import collections
 import ctypes
-import os
 import struct
-import threading
 import zlib
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -29,8 +26,9 @@ import torch
 from . import _lib
 from ._lib import PPYoloHipError, lib
 from ._lib import check as _check
+from .hostio import MAX_THREADS      # noqa: F401 (re-exported)
+from .hostio import HostPool, ImreadMixin, StagingRing, check_outputs, read_bytes, row_pitch
 
-MAX_THREADS = 16
 SIGNATURE = b'\x89PNG\r\n\x1a\n'
 CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
 DEPTHS = {0: (1, 2, 4, 8, 16), 2: (8, 16), 3: (1, 2, 4, 8), 4: (8, 16), 6: (8, 16)}
@@ -46,15 +44,6 @@ class Refusal(Exception):
 
 
 Header = collections.namedtuple('Header', 'width height depth ctype interlace palette idat passes expected')
-
-
-def _bytes(item):
-    if isinstance(item, (bytes, bytearray, memoryview)):
-        return bytes(item)
-    if isinstance(item, (str, os.PathLike)):
-        with open(item, 'rb') as fh:
-            return fh.read()
-    raise PPYoloHipError('expected bytes, a memoryview or a path, got %s' % type(item).__name__)
 
 
 def row_bytes(cols, ctype, depth):
@@ -198,62 +187,30 @@ class HostBatch(object):
     __slots__ = ('n', 'descs', 'sizes', 'stage', 'slot', 'gen', 'table_bytes', 'total_bytes')
 
 
-class PngDecoder(object):
+class PngDecoder(ImreadMixin):
     def __init__(self, device='cuda', threads=None, max_pixels=1 << 28):
         """threads: workers of the host stage, default min(16, images of the call); never more than 16, never derived from
         the machine's CPU count.  max_pixels: a header that claims more is refused before any buffer is sized from it (a
         60-byte file can claim 65535 x 65535)."""
         self.device = torch.device(device)
-        if threads is not None and threads < 1:
-            raise PPYoloHipError('threads must be >= 1')
-        self.threads = None if threads is None else min(int(threads), MAX_THREADS)
+        self._host = HostPool(threads, 'ppy-png')
+        self.threads = self._host.threads
         self.max_pixels = int(max_pixels)
-        self._pool = None
-        self._stage = [None, None]      # pinned uint8 buffers, used in turn
-        self._busy = [None, None]       # event recorded after the copy out of each
-        self._held = [False, False]
-        self._gen = [0, 0]
-        self._turn = 0
-        self._lock = threading.Lock()
+        self._ring = StagingRing(self.device, 1 << 20, stage='host')        # host_decode and reconstruct may run on two threads
 
     # ---- host stage ---------------------------------------------------------------------------------------------------
     def _staging(self, nbytes):
-        with self._lock:
-            s = self._turn if not self._held[self._turn] else self._turn ^ 1
-            if self._held[s]:
-                raise PPYoloHipError('both staging buffers belong to batches that wait for reconstruct(): the host stage may '
-                                     'run at most two batches ahead; reconstruct() or release() one first')
-            self._held[s] = True
-            self._gen[s] += 1
-            gen = self._gen[s]
-            self._turn = s ^ 1
-            busy, self._busy[s] = self._busy[s], None
-        if busy is not None:                    # the last copy out of this buffer
-            busy.synchronize()
-        if self._stage[s] is None or self._stage[s].numel() < nbytes:
-            t = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8)
-            self._stage[s] = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
-        return s, gen, self._stage[s]
+        return self._ring.take(nbytes)
 
     def release(self, hb):
         """Give back the staging buffer of a HostBatch that will not be reconstructed."""
-        with self._lock:
-            if self._gen[hb.slot] == hb.gen:
-                self._held[hb.slot] = False
-
-    def _map(self, fn, n):
-        workers = min(self.threads or MAX_THREADS, n)
-        if workers <= 1:
-            return [fn(i) for i in range(n)]
-        if self._pool is None:
-            self._pool = ThreadPoolExecutor(max_workers=self.threads or MAX_THREADS, thread_name_prefix='ppy-png')
-        return list(self._pool.map(fn, range(n)))
+        self._ring.release(hb.slot, hb.gen)
 
     def refusal(self, item):
         """The chunk walk only, nothing is inflated: None if decode() would take the item as far as its chunks tell, otherwise
         (kind, reason) with kind 'unsupported' or 'corrupt'.  Damage inside the IDAT data still surfaces in decode()."""
         try:
-            parse(_bytes(item), self.max_pixels)
+            parse(read_bytes(item), self.max_pixels)
         except Refusal as r:
             return r.kind, r.reason
         return None
@@ -261,7 +218,7 @@ class PngDecoder(object):
     def host_decode(self, items):
         """Host only: walk, validate and inflate every item into a pinned staging buffer -> HostBatch (jpeg.JpegDecoder's
         entropy_decode: the batch owns the buffer until reconstruct(hb) or release(hb); may run on another thread)."""
-        datas = [_bytes(it) for it in items]
+        datas = [read_bytes(it) for it in items]
         n = len(datas)
         if n == 0:
             raise PPYoloHipError('empty batch')
@@ -297,7 +254,7 @@ class PngDecoder(object):
             return None
 
         try:
-            for i, r in enumerate(self._map(one, n)):
+            for i, r in enumerate(self._host.map(one, n)):
                 if r is not None:
                     raise PPYoloHipError('item %d: %s' % (i, r))
         except BaseException:
@@ -313,31 +270,13 @@ class PngDecoder(object):
         n = hb.n
         if out is None:
             out = [torch.empty((h, w, 3), dtype=torch.uint8, device=self.device) for h, w in hb.sizes]
-        if len(out) != n:
-            raise PPYoloHipError('%d output tensors for %d images' % (len(out), n))
-        for i, (t, (h, w)) in enumerate(zip(out, hb.sizes)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or tuple(t.shape) != (h, w, 3):
-                raise PPYoloHipError('output %d must be a uint8 device tensor [%d, %d, 3]' % (i, h, w))
-            if t.stride(2) != 1 or t.stride(1) != 3 or (h > 1 and t.stride(0) < 3 * w):
-                raise PPYoloHipError('output %d: strides %s: an output needs pixel stride 3, channel stride 1 and rows that do not '
-                                     'overlap (any row pitch)' % (i, tuple(t.stride())))
-        with self._lock:
-            if self._gen[hb.slot] != hb.gen:
-                raise PPYoloHipError('stale HostBatch: its staging buffer has been handed to a later batch')
-            self._held[hb.slot] = True
-            busy = self._busy[hb.slot]
-        if busy is not None:                    # the same HostBatch again: its last copy still reads the table
-            busy.synchronize()
-        _check(L.ppy_png_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
-                                    (ctypes.c_longlong * n)(*[max(t.stride(0), 3 * t.shape[1]) for t in out]),
-                                    hb.stage.data_ptr(), hb.table_bytes), 'ppy_png_pack_table')
-        blob = torch.empty(hb.total_bytes, dtype=torch.uint8, device=self.device)
-        blob.copy_(hb.stage[:hb.total_bytes], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        with self._lock:
-            self._busy[hb.slot] = ev
-            self._held[hb.slot] = False
+        else:
+            check_outputs(out, hb.sizes, self.device)
+        with self._ring.uploading(hb.slot, hb.gen) as staging:
+            _check(L.ppy_png_pack_table(n, hb.descs, (ctypes.c_void_p * n)(*[t.data_ptr() for t in out]),
+                                        (ctypes.c_longlong * n)(*[row_pitch(t) for t in out]),
+                                        hb.stage.data_ptr(), hb.table_bytes), 'ppy_png_pack_table')
+            blob = staging.copy(hb.total_bytes)
         ws_bytes = L.ppy_png_workspace_bytes(n, hb.descs)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=self.device)
         _check(L.ppy_png_reconstruct_u8(n, hb.descs, blob.data_ptr(), blob.data_ptr() + hb.table_bytes, hb.total_bytes - hb.table_bytes,
@@ -353,9 +292,3 @@ class PngDecoder(object):
         except BaseException:
             self.release(hb)                # (outputs refused: the batch never reached the device)
             raise
-
-    def imdecode(self, buf):
-        return self.decode([buf])[0]
-
-    def imread(self, path):
-        return self.decode([path])[0]

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import PPYoloHipError
+from .hostio import Staging, check_image, row_pitch
 
 NEAREST, LANCZOS, BILINEAR, BICUBIC, BOX, HAMMING = range(6)      # Pillow's codes, the ones the reference's `interp` carries
 
@@ -22,71 +23,41 @@ def check_filter(filter, what='filter'):
     return int(filter)
 
 
-def _same_device(a, b):
-    return a.type == b.type and (a.index is None or b.index is None or a.index == b.index)
-
-
 class PilPlanner(object):
     """The host half of a launch, shared by PilResizer and Preprocessor: plans a batch into the pinned staging buffer, copies the
     blob to the device and sizes the workspace.  One staging buffer: planning the next batch first waits on the host for the
-    copy of the batch before it (not for its launches), as BoxDrawer does."""
+    copy of the batch before it (not for its launches; hostio.Staging)."""
 
     def __init__(self, filter, device):
         self.filter = check_filter(filter)
         self.device = torch.device(device)
-        self._stage = None              # pinned host buffer the planner writes into
-        self._busy = None               # event recorded after the last copy out of it
+        self._staging = Staging(self.device, 1 << 16, factor=2)     # the planner writes into it
         self._ws = None                 # device workspace: the uint8 intermediates
         self._keep = None               # what the launches in flight read
-
-    def _alloc(self, nbytes):
-        if self._stage is None or self._stage.numel() < nbytes:
-            t = torch.empty(max(2 * nbytes, 1 << 16), dtype=torch.uint8)
-            self._stage = t.pin_memory() if self.device.type == 'cuda' and torch.cuda.is_available() else t
-        return self._stage.data_ptr()
 
     def plan(self, images, ow, oh):
         """images: uint8 [h,w,3] tensors on self.device with pixel stride 3.  Returns (n, host address of the blob, its device
         copy, blob bytes, workspace or None)."""
-        if self._busy is not None:
-            self._busy.synchronize()
-        descs = [(t.data_ptr(), max(t.stride(0), 3 * t.shape[1]), t.shape[0], t.shape[1]) for t in images]
-        nbytes, ws_bytes = ops.pil_resize_plan(descs, ow, oh, self.filter, self._alloc)
-        blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        blob.copy_(self._stage[:nbytes], non_blocking=True)
-        self._busy = torch.cuda.Event()
-        self._busy.record()
+        descs = [(t.data_ptr(), row_pitch(t), t.shape[0], t.shape[1]) for t in images]
+        nbytes, ws_bytes = ops.pil_resize_plan(descs, ow, oh, self.filter, lambda nb: self._staging.acquire(nb).data_ptr())
+        blob = self._staging.upload(nbytes)
         if ws_bytes and (self._ws is None or self._ws.numel() < ws_bytes):
             self._ws = torch.empty(max(ws_bytes, 1 << 20), dtype=torch.uint8, device=self.device)
         cur = torch.cuda.current_stream(self.device)
         for t in list(images) + ([self._ws] if ws_bytes else []):      # memory another stream's decoder or lane may own
             t.record_stream(cur)
         self._keep = (blob, list(images), self._ws)
-        return len(images), self._stage.data_ptr(), blob, nbytes, (self._ws if ws_bytes else None)
+        return len(images), self._staging.buffer.data_ptr(), blob, nbytes, (self._ws if ws_bytes else None)
 
 
 def device_source(i, im, device):
-    """One source -> a uint8 [h,w,3] tensor on `device` the kernels read where it lies (pixel stride 3, channel stride 1, any row
-    pitch: a decoder output or a crop `big[3:3+h, 5:5+w]`); a numpy array is uploaded; anything else raises with the reason."""
+    """One source -> a uint8 [h,w,3] tensor on `device` the kernels read where it lies (hostio.check_image); a numpy array is
+    uploaded; anything else raises with the reason."""
     if isinstance(im, np.ndarray):
         if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
             raise PPYoloHipError('image %d: numpy %s %s, expected uint8 [h, w, 3]' % (i, im.dtype, tuple(im.shape)))
         return torch.from_numpy(np.ascontiguousarray(im)).to(device, non_blocking=False)
-    if not isinstance(im, torch.Tensor):
-        raise PPYoloHipError('image %d: expected a uint8 [h, w, 3] device tensor or numpy array, got %s' % (i, type(im).__name__))
-    if im.dtype != torch.uint8:
-        raise PPYoloHipError('image %d: dtype %s, expected uint8' % (i, im.dtype))
-    if im.dim() != 3 or im.shape[2] != 3:
-        raise PPYoloHipError('image %d: shape %s, expected [h, w, 3]' % (i, tuple(im.shape)))
-    if not _same_device(im.device, device):
-        raise PPYoloHipError('image %d lives on %s, the resizer on %s: upload it, or pass the numpy array' % (i, im.device, device))
-    h, w = im.shape[:2]
-    if h < 1 or w < 1:
-        raise PPYoloHipError('image %d: %d x %d, width and height must be in 1..65535' % (i, w, h))
-    if im.stride(1) != 3 or im.stride(2) != 1 or (h > 1 and im.stride(0) < 3 * w):
-        raise PPYoloHipError('image %d: strides %s: reading in place needs pixel stride 3, channel stride 1 and a row pitch of at '
-                             'least 3 * w' % (i, tuple(im.stride())))
-    return im
+    return check_image(i, im, device, 'source')
 
 
 class PilResizer(object):

@@ -50,6 +50,22 @@ def same(got, want):
         assert a.shape == b.shape and np.array_equal(a, b), 'image %d: %d pixels differ' % (i, int((a != b).any(axis=2).sum()))
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason='needs two visible devices')
+def test_another_cards_memory_is_refused_by_every_object_built_with_an_unindexed_device():
+    """hostio.same_device: 'cuda' is the current device, so a tensor on cuda:1 is refused while device 0 is current, not read or
+    drawn on from device 0's stream."""
+    from ppyolo_hip._lib import PPYoloHipError
+    from ppyolo_hip.jpeg import JpegEncoder
+    from ppyolo_hip.resize import BICUBIC, PilResizer
+    assert torch.cuda.current_device() == 0
+    far = torch.zeros((8, 9, 3), dtype=torch.uint8, device='cuda:1')
+    dets, count = torch.zeros((1, 1, 6), device='cuda'), torch.zeros((1,), dtype=torch.int32, device='cuda')
+    for call in (lambda: PilResizer(BICUBIC, 'cuda')([far], size=(4, 4)), lambda: drawer()([far], dets, count),
+                 lambda: JpegEncoder(device='cuda').encode([far])):
+        with pytest.raises(PPYoloHipError, match='image 0: lives on cuda:1'):
+            call()
+
+
 def test_seeded_scenes_in_one_batch():
     scenes = [draw_ref.scene(s) for s in range(SCENES)]
     images, rows, counts = [s[0] for s in scenes], [s[1] for s in scenes], [s[2] for s in scenes]

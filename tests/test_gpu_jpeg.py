@@ -139,6 +139,21 @@ def test_host_batches_own_their_staging_buffer():
     assert np.array_equal(d.reconstruct(e1)[0].cpu().numpy(), F.pixels('c422_37x53'))
 
 
+def test_refused_outputs_give_their_staging_buffer_back():
+    """decode() with an `out=` that reconstruct() refuses: the batch never reached the device, so its buffer is free again.
+    Three refusals in a row (there are two buffers), then three good decodes, so both buffers come round."""
+    from ppyolo_hip._lib import PPYoloHipError
+    from ppyolo_hip.jpeg import JpegDecoder
+    d = JpegDecoder()
+    data, want = F.data('c420_5x5'), F.pixels('c420_5x5')
+    for shape in ((5, 4, 3), (4, 5, 3), (5, 5, 4)):
+        with pytest.raises(PPYoloHipError, match=r'output 0 must be a uint8 device tensor \[5, 5, 3\]'):
+            d.decode([data], out=[torch.empty(shape, dtype=torch.uint8, device='cuda')])
+    for _ in range(3):
+        got = d.decode([data])[0].cpu().numpy()
+        assert np.array_equal(got, want) and F.matches_golden('c420_5x5', got)
+
+
 def test_max_pixels():
     from ppyolo_hip._lib import PPYoloHipError
     from ppyolo_hip.jpeg import JpegDecoder

@@ -94,6 +94,38 @@ def test_outputs_are_refused_by_name(dec):
     assert dec.decode([data], out=[ok])[0] is ok and np.array_equal(ok.cpu().numpy(), C.want('fmt_c2_d8'))
 
 
+def test_host_batches_own_their_staging_buffer():
+    """tests/test_gpu_jpeg.py's test of the same name for PngDecoder: a third waiting batch is refused, a refused file gives its
+    buffer back, the same batch may be reconstructed twice, a released or overtaken batch is stale."""
+    from ppyolo_hip._lib import PPYoloHipError
+    from ppyolo_hip.png import PngDecoder
+    cases = C.all_cases()
+    names = ['edge_c2_d8_1x1_first0', 'edge_c0_d8_2x2_first4', 'edge_c6_d16_1x9_first1', 'edge_c2_d8_9x1_first2', 'edge_tie3_wrap']
+
+    def same(hb, name):
+        return _differences(d.reconstruct(hb)[0], C.want(name), name) is None
+
+    d = PngDecoder()
+    a = d.host_decode([cases[names[0]]])
+    b = d.host_decode([cases[names[1]]])
+    with pytest.raises(PPYoloHipError, match='the host stage may run at most two batches ahead'):
+        d.host_decode([cases[names[2]]])
+    assert same(b, names[1])
+    with pytest.raises(PPYoloHipError, match='item 0: corrupt PNG'):    # a refused file gives its buffer back
+        d.host_decode([sorted(C.damaged().items())[0][1][0]])
+    assert same(a, names[0])
+    assert same(a, names[0])                                            # again, while it is still the buffer's batch
+    c = d.host_decode([cases[names[2]]])
+    d.release(c)
+    e1 = d.host_decode([cases[names[3]]])
+    e2 = d.host_decode([cases[names[4]]])
+    assert all((h.slot, h.gen) not in ((e1.slot, e1.gen), (e2.slot, e2.gen)) for h in (a, b, c))
+    for h in (a, b, c):
+        with pytest.raises(PPYoloHipError, match='stale HostBatch'):
+            d.reconstruct(h)
+    assert same(e2, names[4]) and same(e1, names[3])
+
+
 def test_a_corrupt_item_is_named(dec):
     from ppyolo_hip._lib import PPYoloHipError
     cases = C.all_cases()
