@@ -461,7 +461,10 @@ class Replay(object):
                 ref[:, r, s, :] = d2.t() @ xt
                 sq[:, r, s, :] = (d2 * d2).t() @ (xt * xt)
                 if f16:
-                    floor[:, r, s, :] = fk.view(K, 1) + (xt.abs() * ad).sum(dim=0).view(1, C)
+                    # (a tap / channel whose x is zero at every pixel -- padding only, as the off-centre taps of a 1 x 1 map -- is a sum
+                    # of exact zeros whatever the operand scale: no floor, the result must be exactly 0)
+                    live = (xt.abs().sum(dim=0) > 0).view(1, C)
+                    floor[:, r, s, :] = (fk.view(K, 1) + (xt.abs() * ad).sum(dim=0).view(1, C)) * live
         u_fmt, u_floor = (U22, U_FLOOR_F16) if f16 else (U22, 0.0)
         self.compare('wgrad (k=%d)' % P, got, ref, contraction_bound(ref, sq.clamp_min(0).sqrt(), floor, P, u_fmt, u_floor))
         return out
@@ -904,7 +907,8 @@ class Replay(object):
         m, sc = a['mask'], a['scale']
         self.meta(geom=tuple(m.shape), family='random', kind='misc')
         out = call()
-        torch.cuda.synchronize()
+        if m.is_cuda:
+            torch.cuda.synchronize()
         ok = bool(((m == 0) | (m == 1)).all())
         if not ok:
             self.fail('mask values not in {0, 1}')

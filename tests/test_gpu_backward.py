@@ -26,11 +26,7 @@ def _rel(a, b):
     return ((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30)).item()
 
 
-CASES = [  # N, H, W, C, K, R, stride: head layer shapes at small maps + ragged ones
-    (2, 19, 19, 512, 1024, 3, 1), (2, 19, 19, 1024, 512, 1, 1), (2, 19, 19, 1024, 258, 1, 1), (1, 38, 38, 256, 512, 3, 1),
-    (2, 12, 12, 128, 258, 1, 1), (3, 7, 5, 64, 96, 3, 1), (1, 9, 9, 32, 40, 3, 1), (2, 6, 6, 96, 255, 1, 1), (1, 1, 1, 64, 64, 1, 1),
-    (2, 11, 3, 160, 33, 3, 1), (5, 2, 2, 32, 130, 3, 1),
-]
+from train_edge_cases import BACKWARD_CASES as CASES      # noqa: E402  N, H, W, C, K, R, stride: head layer shapes at small maps + ragged ones
 
 
 @pytest.mark.parametrize('case', CASES)

@@ -1,10 +1,11 @@
 """Training-step operators (csrc/train.hip, csrc/yolo_loss.hip) through the C ABI against torch
 autograd on the CPU (= what the reference's backward is), the training oracle (oracle/train_oracle.py) and the gradients the
 REFERENCE produced in its own step (golden g12: d loss / d head outputs, loss terms)."""
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from train_edge_cases import dropblock_mask_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -110,16 +111,7 @@ def test_dropblock_mask_odd_shapes(shape):
     mask, scale = torch.zeros(N, H, W, C).cuda(), torch.zeros(1).cuda()
     ops.dropblock_mask(mask, scale, keep, seed)
     torch.cuda.synchronize()
-    ids = np.arange(N * H * W * C, dtype=np.uint64)
-    with np.errstate(over='ignore'):
-        key = (np.uint64(seed) ^ (ids * np.uint64(0xD1342543DE82EF95))) + np.uint64(0x9E3779B97F4A7C15)
-        key = (key ^ (key >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        key = (key ^ (key >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        key = (key ^ (key >> np.uint64(31))) >> np.uint64(32)
-    u = ((key >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).reshape(N, H, W, C)
-    gamma = np.float32(H * H * (1 - keep)) / np.float32(9 * (H - 2) ** 2)
-    seeds = torch.from_numpy((u < gamma).astype(np.float32)).permute(0, 3, 1, 2)
-    want = 1.0 - F.max_pool2d(seeds, 3, 1, 1)
+    want = dropblock_mask_reference(N, H, W, C, keep, seed)
     assert torch.equal(nchw(mask.cpu()), want)
     if float(want.sum()) > 0:
         assert abs(float(scale) - mask.numel() / float(want.sum())) <= 1e-6 * float(scale)
@@ -133,17 +125,7 @@ def test_dropblock_mask_and_apply():
     mask, scale = torch.zeros(N, H, W, C).cuda(), torch.zeros(1).cuda()
     ops.dropblock_mask(mask, scale, keep, seed)
     torch.cuda.synchronize()
-    ids = np.arange(N * H * W * C, dtype=np.uint64)
-    M = np.uint64(0xFFFFFFFFFFFFFFFF)
-    with np.errstate(over='ignore'):
-        key = (np.uint64(seed) ^ (ids * np.uint64(0xD1342543DE82EF95))) + np.uint64(0x9E3779B97F4A7C15)
-        key = (key ^ (key >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        key = (key ^ (key >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        key = (key ^ (key >> np.uint64(31))) >> np.uint64(32)
-    u = ((key >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).reshape(N, H, W, C)
-    gamma = np.float32(H * H * (1 - keep)) / np.float32(9 * (H - 2) ** 2)
-    seeds = torch.from_numpy((u < gamma).astype(np.float32)).permute(0, 3, 1, 2)
-    want = 1.0 - F.max_pool2d(seeds, 3, 1, 1)
+    want = dropblock_mask_reference(N, H, W, C, keep, seed)
     assert torch.equal(nchw(mask.cpu()), want)
     assert abs(float(scale) - mask.numel() / float(want.sum())) <= 1e-6 * float(scale)
     frac = 1.0 - float(want.mean())
