@@ -5,8 +5,10 @@ canvas(recipe): the pre-resize image of a planned sample, computed the way the r
 own dtype rules), from the uint8 BGR sources.  tests/test_augment_plan.py pins it to the reference (g19_augment).
 
 resize(canvas, recipe): cv2.resize as OpenCV 4.x's scalar templates compute it, applied with the planner's coefficient
-tables (augment.resize_plan).  UNPINNED: cv2 is not installed in this image; the restated 8-bit CUBIC is checked against
-oracle/preprocess_oracle.py, the rest only against the device kernel.
+tables (augment.resize_plan).  PINNED: the tables against the interpolations' definitions in float64, to the measured bound of
+tests/test_augment_cases.py (profiles/augment_resize_definition.txt); the 8-bit tables as the rounded float tables; the restated
+8-bit CUBIC against oracle/preprocess_oracle.py.  NOT PINNED: OpenCV's own rounding inside its scalar templates (work types,
+accumulation order, the 8-bit and integer-scale AREA roundings) -- cv2 is not installed in this image.
 
 normalize(img): NormalizeImage + Permute of the reference (float32 / 255, float64 mean / std, rounded to float32)."""
 import numpy as np

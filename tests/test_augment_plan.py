@@ -1,7 +1,8 @@
 """The training-batch planner (ppyolo_hip/augment.py) against the reference's own training reader (g19_augment, made by
 tools/make_goldens.py g19 with the reference's transform classes): every draw, recipe, final box array and the final
-np.random state, bit for bit; the CPU restatement's canvases and normalisation against the reference's.  The resize is
-UNPINNED (no cv2 in this image): only its 8-bit CUBIC restatement is checked here, against oracle/preprocess_oracle.py."""
+np.random state, bit for bit; the CPU restatement's canvases and normalisation against the reference's.  Of the resize,
+the 8-bit CUBIC restatement is checked here against oracle/preprocess_oracle.py; tests/test_augment_cases.py checks the
+coefficient tables against the interpolations' definitions (what stays unpinned without cv2: see tests/augment_ref.py)."""
 import numpy as np
 import pytest
 

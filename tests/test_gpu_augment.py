@@ -1,7 +1,13 @@
 """Training batches on the device (ppyolo_hip/augment.py, csrc/augment.hip).  The canvas kernel is pinned to the reference
-(g19_augment); the render kernel is compared bit for bit with the CPU restatement tests/augment_ref.py, whose resize is
-UNPINNED (no cv2 in this image); the target kernel with targets.gt2yolo_target; the builder with the CPU chain and in
-the reference's training call."""
+(g19_augment); the render kernel is compared bit for bit with the CPU restatement tests/augment_ref.py; the target kernel with
+targets.gt2yolo_target; the builder with the CPU chain and in the reference's training call.  The hand-built edge recipes are
+in tests/test_gpu_augment_edges.py.
+
+What pins the restatement's resize: the planner's coefficient tables are checked against the interpolations' definitions in
+float64, to the measured bound of tests/test_augment_cases.py (profiles/augment_resize_definition.txt); the 8-bit tables are
+the rounded float tables; the restated 8-bit CUBIC equals oracle/preprocess_oracle.py.  NOT pinned: OpenCV's own rounding
+inside its scalar templates (work types, accumulation order, the 8-bit and integer-scale AREA roundings), which only cv2 could
+confirm and cv2 is not installed here."""
 import numpy as np
 import pytest
 import torch
@@ -11,6 +17,7 @@ from conftest import build_train_model
 from config import PPYOLO_2x_Config, PPYOLO_r18vd_Config
 from ppyolo_hip import augment as A, ops, targets as T
 from ppyolo_hip._lib import PPYoloHipError, lib
+from test_augment_cases import TARGET_S, gt2yolo_loop, target_edge_boxes, target_edge_variants
 from test_augment_plan import golden_batches, plan_batch
 
 pytestmark = pytest.mark.gpu
@@ -84,6 +91,26 @@ def test_target_kernel_equals_gt2yolo_target(cfgc):
         flat = torch.full((sum(r.size for r in ref),), 7.0, device='cuda')
         ops.augment_targets(flat, dev, lay['toff'], lay['tval'], len(o))
         assert torch.equal(flat.cpu(), torch.from_numpy(np.concatenate([r.ravel() for r in ref])))
+
+
+@pytest.mark.parametrize('cfgc', [PPYOLO_2x_Config, PPYOLO_r18vd_Config])
+def test_target_kernel_on_the_edge_boxes(cfgc):
+    """Centres on a cell boundary, at 0 and at the largest float32 below 1, an exact tie of two anchors, a zero-width and a
+    zero-score box, iou_thresh = 0.7 with one box on two anchors of a level (tests/test_augment_cases.py builds them and checks
+    the same on the CPU): the records scattered by the device equal gt2yolo_target, and both equal the per-box loop."""
+    g = cfgc().gt2YoloTarget
+    bb, cl, sc = target_edge_boxes(g)
+    for name, anchors, thr in target_edge_variants(g):
+        args = (bb, cl, sc, anchors, g['anchor_masks'], g['downsample_ratios'], g['num_classes'], TARGET_S, thr)
+        ref = T.gt2yolo_target(*args)
+        o, v = T.gt2yolo_records(*args)
+        blob, lay = A.pack_batch([], True, o, v, None, None, None)
+        dev = torch.from_numpy(blob).cuda()
+        flat = torch.full((sum(r.size for r in ref),), 7.0, device='cuda')
+        ops.augment_targets(flat, dev, lay['toff'], lay['tval'], len(o))
+        got = flat.cpu().numpy()
+        assert got.dtype == np.float32 and np.array_equal(got, np.concatenate([r.ravel() for r in ref])), name
+        assert np.array_equal(got, np.concatenate([r.ravel() for r in gt2yolo_loop(*args)])), name
 
 
 def _cpu_chain(b, recipes, bb, cl, sc, S):
