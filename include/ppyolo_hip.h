@@ -448,6 +448,46 @@ int ppy_pil_resize_u8(int n, const void *h_blob, const void *blob, size_t blob_b
 int ppy_preprocess_pil_u8_f32(int n, const void *h_blob, const void *blob, size_t blob_bytes, void *ws, size_t ws_bytes,
                               int swap_rb, const float *lut /* device [3][256] */, float *out, void *stream);
 
+/* Crops of detections: Pillow's Image.resize((ow, oh), filter, box=(x0, y0, x1, y1)) with the boxes read ON THE DEVICE
+ * (csrc/pil_crop.hip), bit for bit with Pillow 12.2.0.  One call resizes up to cap crops of a batch
+ * of n images to one (ow, oh) with one filter in four launches on `stream` (select, plan, horizontal, vertical), without a
+ * host synchronisation: every grid is sized from n, K or M, ow, oh and the image sizes.  The box reaches the arithmetic as
+ * four float32; per axis scale = (double)(in1 - in0) / out with the subtraction in float32, the taps are clamped to the
+ * IMAGE, not to the box (so this is not crop().resize()), the horizontal pass runs on the source rows the vertical taps
+ * read, and a pass is skipped iff its axis keeps its size and the box is the whole axis.
+ *
+ * Rows form (ppy_pil_crop_rows_u8): dets = device float32 [n][K][6] rows (class, score, x0, y0, x1, y1), count = device int32
+ * [n], as forward_padded returns them; cap = n * K.  Row r < min(count[i], K) of image i is taken iff all six values are
+ * finite, class >= 0, score >= thresh, 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h for the row's own box and for the padded
+ * one, and fewer than top_k rows of image i were taken before it.  Padding, in float32 with one rounding per operation:
+ * bw = x1 - x0, x0' = max(x0 - pad * bw, 0), x1' = min(x1 + pad * bw, w); y likewise.
+ * List form (ppy_pil_crop_list_u8): boxes_in = device float32 [M][4], image = device int32 [M]; cap = M.  An entry is taken
+ * iff its image index is in 0..n-1 and its box passes the same test; the list's order is kept.
+ * Outputs (device): out uint8 [cap][oh][ow][3], zero past the end; src int32 [cap][2] = (image, row or list index) in
+ * image-major, row-ascending order, -1 past the end; total int32 [1]; boxes float32 [cap][4] = the boxes that were resized,
+ * 0 past the end.  The order comes from an ordered scan in one workgroup: it does not depend on scheduling.
+ *
+ * ppy_pil_crop_plan_bytes (HOST only, no GPU call): validates the batch and returns the workspace size in *ws_bytes and the
+ * taps reserved per output sample of the x and y axis in ksize_cap[2] (either may be NULL).  form: 0 rows (rows_or_m = K),
+ * 1 list (rows_or_m = M; pad and top_k are not read).  With kx = ksize of (largest width -> ow), ky = ksize of (largest
+ * height -> oh) (0 for NEAREST), A(v) = v rounded up to 256:
+ *   ws_bytes = A(32 cap) + A(4 cap) + A(4 cap ow (2 + kx)) + A(4 cap oh (2 + ky)) + cap A(largest height * A16(3 ow)).
+ * Limits, refused and never clamped (PPY_ERR_UNSUPPORTED; h_reason, NULL or 96 chars, names the value): an input side
+ * outside 1..65535, an output side outside 1..8192, kx or ky > 1024, a filter outside 0..5, an image with h > 100 * w
+ * (Pillow resizes those vertically first), n * K or M outside 1..65536, pad outside [0, 4] or not finite, top_k < 1.
+ * n outside 1..1024, a null pointer or a pitch below 3 * w: PPY_ERR_BAD_ARG.  A workspace that is NULL or too small:
+ * PPY_ERR_WORKSPACE.
+ * TRUST BOUNDARY: h_images (HOST) is validated and sizes the grids and the workspace; the kernels read `images`, its DEVICE
+ * copy, and the device rows without further checks beyond keeping every access inside the images and the workspace. */
+int ppy_pil_crop_plan_bytes(int n, const ppy_pil_image_t *h_images, int form, int rows_or_m, int ow, int oh, int filter,
+                            float pad, int top_k, size_t *ws_bytes, int *ksize_cap, char *h_reason);
+int ppy_pil_crop_rows_u8(int n, const ppy_pil_image_t *h_images, const ppy_pil_image_t *images, const float *dets,
+                         const int *count, int K, float thresh, float pad, int top_k, int ow, int oh, int filter, void *ws,
+                         size_t ws_bytes, unsigned char *out, int *src, int *total, float *boxes, void *stream);
+int ppy_pil_crop_list_u8(int n, const ppy_pil_image_t *h_images, const ppy_pil_image_t *images, const float *boxes_in,
+                         const int *image, int M, int ow, int oh, int filter, void *ws, size_t ws_bytes, unsigned char *out,
+                         int *src, int *total, float *boxes, void *stream);
+
 /* Training batches (ppyolo_hip/augment.py TrainBatchBuilder): the reference's training reader (train.py:36-152) with
  * the transforms of config/ppyolo_2x.py:154-251, planned on the host.  blob: DEVICE copy of the planner's upload (8-byte
  * aligned, blob_bytes long): n per-sample descriptors (augment.hip struct AugSample, 328 bytes each) at offset 0, then

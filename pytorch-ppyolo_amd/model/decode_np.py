@@ -141,3 +141,40 @@ class Decode(object):
         dets, count = dets.cpu().numpy(), count.cpu().tolist()
         empty = (np.array([]), np.array([]), np.array([]))
         return files, [self._split(d[:c]) if c > 0 else empty for d, c in zip(dets, count)]
+
+    def crop_files(self, paths_or_bytes, size, filter=3, pad=0.0, draw_thresh=None, decoder=None, encoder=None):
+        """From file to one JPEG file per detection: JPEG paths / byte strings -> (per image the list of JPEG bytes of its
+        detections with score >= draw_thresh, in row order, each resized to size = (ow, oh) with Pillow's `filter` (default
+        BICUBIC) and `pad`; per image (boxes, scores, classes) as annotate_files returns them).  decode -> preprocess ->
+        forward_padded -> DetectionCropper -> JpegEncoder.encode, on the device: the crops are cut from the undrawn source
+        pixels, the boxes never visit the host, and the first read-back is the crop list's (ppyolo_hip/crops.py)."""
+        from ppyolo_hip.crops import DetectionCropper
+        if draw_thresh is None:
+            draw_thresh = self.cfg.test_cfg['draw_thresh']
+        if decoder is None:
+            if self._jpeg is None:
+                from ppyolo_hip.jpeg import JpegDecoder
+                self._jpeg = JpegDecoder()
+            decoder = self._jpeg
+        if encoder is None:
+            if self._encoder is None:
+                from ppyolo_hip.jpeg import JpegEncoder
+                self._encoder = JpegEncoder()
+            encoder = self._encoder
+        key = (tuple(size), filter, pad)
+        if getattr(self, '_cropper_key', None) != key:
+            self._cropper, self._cropper_key = DetectionCropper(size, filter=filter, pad=pad), key
+        images = decoder.decode(list(paths_or_bytes))
+        pimage, im_size = self._preprocessor()(images)
+        dets, count, _ = self._yolo.forward_padded(pimage, im_size)
+        crops, src, total = self._cropper(images, dets, count, draw_thresh)
+        per_image = self._cropper.split(crops, src, total)
+        flat = [c for _, group in per_image for c in group.unbind(0)]
+        encoded = encoder.encode(flat) if flat else []
+        files, at = [], 0
+        for rows, _ in per_image:
+            files.append(encoded[at:at + len(rows)])
+            at += len(rows)
+        dets, count = dets.cpu().numpy(), count.cpu().tolist()
+        empty = (np.array([]), np.array([]), np.array([]))
+        return files, [self._split(d[:c]) if c > 0 else empty for d, c in zip(dets, count)]

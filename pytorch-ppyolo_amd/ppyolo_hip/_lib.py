@@ -178,6 +178,12 @@ _PROTOS = {
                                     ctypes.c_char_p]),
     'ppy_pil_resize_u8': (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
     'ppy_preprocess_pil_u8_f32': (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_void_p]),
+    'ppy_pil_crop_plan_bytes': (c_int, [c_int, ctypes.POINTER(PilImage), c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_int,
+                                        ctypes.POINTER(c_size_t), ctypes.POINTER(c_int), ctypes.c_char_p]),
+    'ppy_pil_crop_rows_u8': (c_int, [c_int, ctypes.POINTER(PilImage), c_void_p, c_void_p, c_void_p, c_int, ctypes.c_float, ctypes.c_float,
+                                     c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ppy_pil_crop_list_u8': (c_int, [c_int, ctypes.POINTER(PilImage), c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                     c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     'ppy_augment_render_f32': (c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, ctypes.POINTER(c_double), c_int, c_void_p,
                                         c_void_p]),
     'ppy_augment_canvas': (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -576,6 +576,65 @@ def preprocess_pil_images(n, h_blob, blob, nbytes, ws, lut, out, swap_rb=True):
                                           _stream()), 'ppy_preprocess_pil_u8_f32')
 
 
+def pil_crop_descs(images):
+    """images = list of (base, pitch, h, w) -> the ctypes array of ppy_pil_image_t the crop entries take as `h_images`."""
+    descs = (_lib.PilImage * max(len(images), 1))()
+    for d, (base, pitch, h, w) in zip(descs, images):
+        d.base, d.pitch, d.h, d.w = int(base), int(pitch), int(h), int(w)
+    return descs
+
+
+def pil_crop_plan_bytes(descs, n, form, rows_or_m, ow, oh, filter, pad=0.0, top_k=1):
+    """The host validation of a crop call (ppy_pil_crop_plan_bytes; no GPU call): form 0 = rows (rows_or_m = K), 1 = list
+    (rows_or_m = M).  Returns (device workspace bytes, (kx, ky) taps reserved per output sample).  A batch outside the limits
+    raises with the reason, which names the value."""
+    reason = ctypes.create_string_buffer(96)
+    ws_bytes, ks = ctypes.c_size_t(0), (ctypes.c_int * 2)()
+    rc = lib().ppy_pil_crop_plan_bytes(int(n), descs, int(form), int(rows_or_m), int(ow), int(oh), int(filter), float(pad), int(top_k),
+                                       ctypes.byref(ws_bytes), ks, reason)
+    if rc != _lib.OK and reason.value:
+        raise _lib.PPYoloHipError('ppy_pil_crop_plan_bytes refused the batch: %s (code %d)' % (reason.value.decode(), rc))
+    check(rc, 'ppy_pil_crop_plan_bytes')
+    return ws_bytes.value, (ks[0], ks[1])
+
+
+def _pil_crop_outputs(cap, ow, oh, d_images, ws, out, src, total, boxes):
+    _dev(d_images, ws, out, src, total, boxes)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and d_images.dtype == torch.uint8 and d_images.is_contiguous()
+    assert out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (cap, oh, ow, 3)
+    assert src.dtype == torch.int32 and src.is_contiguous() and tuple(src.shape) == (cap, 2)
+    assert total.dtype == torch.int32 and total.numel() == 1
+    assert boxes.dtype == torch.float32 and boxes.is_contiguous() and tuple(boxes.shape) == (cap, 4)
+
+
+def pil_crop_rows_u8(descs, d_images, dets, count, thresh, pad, top_k, ow, oh, filter, ws, out, src, total, boxes):
+    """Crops of detection rows (ppy_pil_crop_rows_u8): descs = the host descriptors, d_images = their device copy (uint8), dets
+    float32 [n, K, 6] and count int32 [n] on the device.  out uint8 [n * K, oh, ow, 3], src int32 [n * K, 2], total int32 [1],
+    boxes float32 [n * K, 4]: all written on the current stream."""
+    n, K = dets.shape[0], dets.shape[1]
+    _dev(dets, count)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[2] == 6
+    assert count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (n,)
+    assert d_images.numel() >= n * ctypes.sizeof(_lib.PilImage)
+    _pil_crop_outputs(n * K, ow, oh, d_images, ws, out, src, total, boxes)
+    check(lib().ppy_pil_crop_rows_u8(n, descs, d_images.data_ptr(), dets.data_ptr(), count.data_ptr(), K, float(thresh), float(pad),
+                                     int(top_k), int(ow), int(oh), int(filter), ws.data_ptr(), ws.numel(), out.data_ptr(), src.data_ptr(),
+                                     total.data_ptr(), boxes.data_ptr(), _stream()), 'ppy_pil_crop_rows_u8')
+
+
+def pil_crop_list_u8(descs, n, d_images, boxes_in, image, ow, oh, filter, ws, out, src, total, boxes):
+    """Crops of a caller's list (ppy_pil_crop_list_u8): boxes_in float32 [M, 4], image int32 [M] on the device."""
+    M = boxes_in.shape[0]
+    _dev(boxes_in, image)
+    assert boxes_in.dtype == torch.float32 and boxes_in.is_contiguous() and tuple(boxes_in.shape) == (M, 4)
+    assert image.dtype == torch.int32 and image.is_contiguous() and tuple(image.shape) == (M,)
+    assert d_images.numel() >= n * ctypes.sizeof(_lib.PilImage)
+    _pil_crop_outputs(M, ow, oh, d_images, ws, out, src, total, boxes)
+    check(lib().ppy_pil_crop_list_u8(int(n), descs, d_images.data_ptr(), boxes_in.data_ptr(), image.data_ptr(), M, int(ow), int(oh),
+                                     int(filter), ws.data_ptr(), ws.numel(), out.data_ptr(), src.data_ptr(), total.data_ptr(),
+                                     boxes.data_ptr(), _stream()), 'ppy_pil_crop_list_u8')
+
+
 def _augment_sources(blob, sources):
     """The host arrays (n_src, ptrs, pitch, h, w) of ppy_augment_*_src for a list of uint8 [h,w,3] device tensors: pixel stride 3,
     any row pitch >= 3 * w, any alignment (a view `big[3:3+h, 5:5+w]` is a source as it lies)."""

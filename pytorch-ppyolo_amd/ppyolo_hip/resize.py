@@ -60,6 +60,31 @@ def device_source(i, im, device):
     return check_image(i, im, device, 'source')
 
 
+def check_boxes(shapes, box):
+    """Pillow's own test of `resize(box=)`, on the host: shapes = [(h, w)], box = one (x0, y0, x1, y1) per image -> float32
+    [n, 4], rounded as Pillow's "(ffff)" rounds them.  A box Pillow refuses raises, naming the image and the value."""
+    try:
+        b = np.array([[float(v) for v in one] for one in box], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise PPYoloHipError('box=%r: expected one (x0, y0, x1, y1) per image' % (box,))
+    if b.shape != (len(shapes), 4):
+        raise PPYoloHipError('box: an array of shape %s for %d images, expected one (x0, y0, x1, y1) per image'
+                             % (b.shape, len(shapes)))
+    with np.errstate(over='ignore'):
+        b = b.astype(np.float32)
+    for i, ((h, w), (x0, y0, x1, y1)) in enumerate(zip(shapes, b)):
+        if not np.isfinite(b[i]).all():
+            raise PPYoloHipError('image %d: box %s is not finite' % (i, tuple(b[i].tolist())))
+        if x0 < 0 or y0 < 0:                # Pillow: "box offset can't be negative"
+            raise PPYoloHipError('image %d: box offset can\'t be negative: (x0, y0) = (%r, %r)' % (i, float(x0), float(y0)))
+        if x1 > w or y1 > h:                # Pillow: "box can't exceed original image size"
+            raise PPYoloHipError('image %d: box can\'t exceed original image size %d x %d: (x1, y1) = (%r, %r)'
+                                 % (i, w, h, float(x1), float(y1)))
+        if not (x0 < x1 and y0 < y1):       # (Pillow refuses x1 < x0 and resizes an empty box to a constant; the kernels skip both)
+            raise PPYoloHipError('image %d: box (%r, %r, %r, %r) is empty' % (i, float(x0), float(y0), float(x1), float(y1)))
+    return b
+
+
 class PilResizer(object):
     """`Image.fromarray(im).resize(size, filter)` for a batch of 3-channel uint8 images of any sizes, on the device."""
 
@@ -67,11 +92,17 @@ class PilResizer(object):
         self.device = torch.device(device)
         self._planner = PilPlanner(filter, self.device)
         self.filter = self._planner.filter
+        self._cropper = None            # the launcher of the box= path (ppyolo_hip/crops.py), made on first use
 
-    def __call__(self, images, size):
+    def __call__(self, images, size, box=None):
         """images: list of uint8 [h,w,3] device tensors (read in place) or numpy arrays (uploaded); size = (ow, oh), Pillow's
         order.  Returns a list of uint8 [oh, ow, 3] device tensors (views of one batch tensor), asynchronous on the current
-        stream: two launches, or one when no image changes its width."""
+        stream: two launches, or one when no image changes its width.
+        box: None, or one (x0, y0, x1, y1) per image, Pillow's `resize(size, filter, box=)`: the values are rounded to float32
+        as Pillow's C does and run through the crop kernels (csrc/pil_crop.hip; four launches).  A box
+        Pillow refuses raises PPYoloHipError naming the image and the value, on the host."""
+        if box is not None:
+            return self._call_box(list(images), size, box)
         images = list(images)
         if not images:
             raise PPYoloHipError('empty batch')
@@ -86,6 +117,20 @@ class PilResizer(object):
         out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device)
         ops.pil_resize_u8(n, h_blob, blob, nbytes, ws, out)
         return list(out.unbind(0))
+
+    def _call_box(self, images, size, box):
+        from . import crops
+        if self._cropper is None:
+            self._cropper = crops.CropLauncher(self.filter, self.device)
+        ow, oh = crops.check_size(size)
+        dev = self._cropper.sources(images)
+        b = check_boxes([(t.shape[0], t.shape[1]) for t in dev], box)
+        n = len(dev)
+        descs, d_images, ws, out, src, total, boxes = self._cropper.prepare(dev, 1, n, ow, oh)
+        d_boxes = torch.from_numpy(b).to(self.device)
+        d_index = torch.arange(n, dtype=torch.int32, device=self.device)
+        ops.pil_crop_list_u8(descs, n, d_images, d_boxes, d_index, ow, oh, self.filter, ws, out, src, total, boxes)
+        return list(out.unbind(0))          # (every box passed the kernels' own test above: crop i is image i)
 
 
 def parse_plan(blob):
