@@ -693,6 +693,41 @@ int ppy_multiclass_nms_f32(const float *boxes, int M_total, int num_classes, con
                            int background_label, float *out_dets, int *out_count, int *out_keep_idx,
                            void *ws, size_t ws_bytes, void *stream);
 
+/* Merge of the rows of a batch of VIEWS (tiled inference: tiles of large images plus the whole image) into one list per
+ * image, in the forward_padded row format (csrc/merge_views.hip).
+ * dets = device float32 [V][K][6] rows (class, score, x0, y0, x1, y1) in view pixel coordinates, count = device int32 [V]
+ * as forward_padded writes them.  The view table [V][3] int32 = (image, ox, oy) is given twice: h_views on the host, where
+ * the limits are checked, and views, its device copy, which the kernel reads.  image = -1 marks a padding view, which is
+ * ignored; the views of an image may lie anywhere in the table; n = the number of images (image < n).
+ *   admission:   row r of view v iff r < min(count[v], K), all six values finite, 0 <= class < 2^24, score >= score_thresh;
+ *                the class id is the truncated value
+ *   translation: x0, x1 += (float)ox, y0, y1 += (float)oy: one fp32 rounding each, no clipping
+ *   order:       per image, score descending as values (-0.0 ties with +0.0), then view ascending, then row ascending
+ *   scan:        greedy in that order: a candidate is selected iff metric(candidate, k) <= thresh for every already selected
+ *                k (class_agnostic = 0: for every selected k of the same class id); a NaN metric suppresses
+ *   metric:      PPY_MERGE_IOU = JaccardOverlap as in ppy_multiclass_nms_f32 with norm = 0; PPY_MERGE_IOS = the same
+ *                disjoint rule, iw, ih and inter, then inter / (area_k < area_candidate ? area_k : area_candidate)
+ *   output:      the first keep_top_k selections in scan order: out_dets [n][keep_top_k][6] = the original class and score and
+ *                the translated box, -1 behind out_count[n]; out_src int32 [n][keep_top_k][2] = (view, row), -1 padding
+ * fp32 with one rounding per operation, no fma; no floating-point atomics: two runs give the same bytes.
+ * Limits, refused and never clamped (PPY_ERR_UNSUPPORTED; h_reason, NULL or 96 chars, names the value): keep_top_k outside
+ * 1..PPY_MERGE_MAX_KEEP, K < 1, an image with more than PPY_MERGE_MAX_ROWS rows ((views of the image) x K), a NaN thresh or
+ * score_thresh, an unknown metric.  A null pointer, n outside 1..65535, V < 1, V x K >= 2^31 or a table entry outside
+ * -1..n-1: PPY_ERR_BAD_ARG.  ws: ppy_merge_views_workspace_bytes(n, V, K) = 32 n min(V K, PPY_MERGE_MAX_ROWS) bytes (the
+ * sorted candidates of every image, 32 bytes each), 16-byte aligned; it carries nothing from one call to the next.
+ * No host synchronisation: one launch on `stream`, one workgroup per image, capturable into a graph. */
+#define PPY_MERGE_IOU 0
+#define PPY_MERGE_IOS 1
+#define PPY_MERGE_MAX_ROWS 8192   /* rows of one image: the keys' stage in LDS                          */
+#define PPY_MERGE_RANK_MAX 1024   /* admitted rows up to which the counting sort orders; beyond: bitonic */
+#define PPY_MERGE_CHUNK 64        /* candidates per step of the greedy scan                              */
+#define PPY_MERGE_MAX_KEEP 1024
+size_t ppy_merge_views_workspace_bytes(int n, int V, int K);
+int ppy_merge_views_f32(const float *dets, const int *count, int V, int K, const int *h_views, const int *views, int n,
+                        int metric, float thresh, float score_thresh, int class_agnostic, int keep_top_k,
+                        float *out_dets, int *out_count, int *out_src, void *ws, size_t ws_bytes, char *h_reason,
+                        void *stream);
+
 /* ------------------------------------------------------------------------------------
  * conv2 -> conv3 of an identity bottleneck in ONE launch (round 5; reference model/resnet_vd.py:81-87:
  * relu(bn3(conv3(relu(bn2(conv2(t))))) + x)): conv A = 3x3 / stride 1 / pad 1, CA -> KA, BatchNorm, ReLU; conv B = 1x1, KA -> KB,

@@ -178,3 +178,31 @@ class Decode(object):
         dets, count = dets.cpu().numpy(), count.cpu().tolist()
         empty = (np.array([]), np.array([]), np.array([]))
         return files, [self._split(d[:c]) if c > 0 else empty for d, c in zip(dets, count)]
+
+    def tiled_detector(self, **kw):
+        """The TiledDetector (ppyolo_hip/tiles.py) of these settings; it is kept, keyed by its settings, as crop_files keeps its
+        cropper."""
+        from ppyolo_hip.tiles import TiledDetector
+        key = tuple(sorted(kw.items()))
+        if getattr(self, '_tiled_key', None) != key:
+            self._tiled, self._tiled_key = TiledDetector(self._yolo, self.cfg, self.target_size, **kw), key
+        return self._tiled
+
+    def detect_tiled(self, images, **kw):
+        """detect_raw for images larger than the network input: every image is cut into overlapping tiles (plus the whole
+        image), the views run through the network at native resolution and their rows are merged on the device.  images: uint8
+        BGR [h,w,3] device tensors (read in place) or numpy arrays; kw: TiledDetector's settings (tile, overlap, full_view, metric,
+        thresh, score_thresh, keep_top_k, class_agnostic, batch).  Returns per image (boxes, scores, classes) in image pixels."""
+        dets, count, _ = self.tiled_detector(**kw)(images)
+        dets, count = dets.cpu().numpy(), count.cpu().tolist()
+        empty = (np.array([]), np.array([]), np.array([]))
+        return [self._split(d[:c]) if c > 0 else empty for d, c in zip(dets, count)]
+
+    def detect_tiled_files(self, paths_or_bytes, decoder=None, **kw):
+        """detect_tiled from the files themselves, decoded on the device as detect_files does."""
+        if decoder is None:
+            if self._jpeg is None:
+                from ppyolo_hip.jpeg import JpegDecoder
+                self._jpeg = JpegDecoder()
+            decoder = self._jpeg
+        return self.detect_tiled(decoder.decode(list(paths_or_bytes)), **kw)

@@ -18,6 +18,8 @@ ERR_UNSUPPORTED = -2      # PPY_ERR_UNSUPPORTED (include/ppyolo_hip.h)
 ACT = {None: 0, 'relu': 1, 'leaky': 2}
 NORM_ACT = dict(ACT, mish=3)      # PPY_ACT_MISH: ppy_group_norm_f32 only (the convolution entry points reject it)
 GN_MAX_CHUNKS = 128               # PPY_GN_MAX_CHUNKS
+MERGE_METRIC = {'iou': 0, 'ios': 1}                                              # PPY_MERGE_IOU / PPY_MERGE_IOS
+MERGE_MAX_ROWS, MERGE_RANK_MAX, MERGE_CHUNK, MERGE_MAX_KEEP = 8192, 1024, 64, 1024      # PPY_MERGE_* (include/ppyolo_hip.h)
 
 
 class PPYoloHipError(RuntimeError):
@@ -225,6 +227,9 @@ _PROTOS = {
                                        c_float, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                        c_void_p]),
     'ppy_multiclass_nms_workspace_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'ppy_merge_views_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'ppy_merge_views_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_float, c_float,
+                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.c_char_p, c_void_p]),
     'ppy_nms_candidates_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p]),
     'ppy_conv3x3_conv1x1_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

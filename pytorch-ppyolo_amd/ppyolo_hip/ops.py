@@ -10,6 +10,7 @@ buffer whose last dimension is the pixel stride `ld`.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -954,6 +955,51 @@ def multiclass_nms(boxes, num_classes, cand_key, cand_idx, cand_count, nms_top_k
                ('nms_eta=%r (supported: 1.0, no adaptive threshold)' % (nms_eta,), float(nms_eta) != 1.0)]
         raise _lib.PPYoloHipError('ppy_multiclass_nms_f32: unsupported ' + ', '.join(t for t, b in bad if b))
     check(rc, 'ppy_multiclass_nms_f32')
+
+
+def merge_views_table(views):
+    """views = a sequence of (image, ox, oy) -> the int32 numpy array [V, 3] merge_views takes as its host table."""
+    tab = np.ascontiguousarray(np.asarray(views, dtype=np.int64).reshape(-1, 3))
+    if tab.size and (np.abs(tab) >= 1 << 31).any():
+        raise _lib.PPYoloHipError('view table: an entry does not fit int32')
+    return tab.astype(np.int32)
+
+
+def merge_views_workspace(n, V, K, device):
+    """Scratch tensor for merge_views: 32 n min(V K, 8192) bytes (empty, which the call then refuses, for n, V or K < 1)."""
+    return torch.empty(int(lib().ppy_merge_views_workspace_bytes(int(n), int(V), int(K))), dtype=torch.uint8, device=device)
+
+
+def merge_views(dets, count, h_views, d_views, n, metric, thresh, score_thresh, class_agnostic, keep_top_k, out_dets, out_count,
+                out_src, ws=None):
+    """Cross-view greedy suppression (ppy_merge_views_f32; include/ppyolo_hip.h has the contract): dets float32 [V, K, 6] and
+    count int32 [V] on the device as forward_padded writes them, h_views = merge_views_table(...) and d_views its device copy
+    (int32 [V, 3]); out_dets float32 [n, keep_top_k, 6], out_count int32 [n], out_src int32 [n, keep_top_k, 2].  One launch on
+    the current stream.  A request outside the limits raises PPYoloHipError naming the value."""
+    if metric not in _lib.MERGE_METRIC:
+        raise _lib.PPYoloHipError("ppy_merge_views_f32: unknown metric %r, known: 'iou', 'ios'" % (metric,))
+    n, keep_top_k = int(n), int(keep_top_k)
+    _dev(dets, count, d_views, out_dets, out_count, out_src)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[2] == 6
+    V, K = dets.shape[0], dets.shape[1]
+    assert count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (V,)
+    assert isinstance(h_views, np.ndarray) and h_views.dtype == np.int32 and h_views.flags.c_contiguous and h_views.shape == (V, 3)
+    assert d_views.dtype == torch.int32 and d_views.is_contiguous() and tuple(d_views.shape) == (V, 3)
+    if 1 <= keep_top_k <= _lib.MERGE_MAX_KEEP and n >= 1:      # (outside: the library refuses by name before it touches them)
+        assert out_dets.dtype == torch.float32 and out_dets.is_contiguous() and tuple(out_dets.shape) == (n, keep_top_k, 6)
+        assert out_count.dtype == torch.int32 and out_count.is_contiguous() and tuple(out_count.shape) == (n,)
+        assert out_src.dtype == torch.int32 and out_src.is_contiguous() and tuple(out_src.shape) == (n, keep_top_k, 2)
+    if ws is None:
+        ws = merge_views_workspace(n, V, K, dets.device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    reason = ctypes.create_string_buffer(96)
+    rc = lib().ppy_merge_views_f32(dets.data_ptr(), count.data_ptr(), V, K, h_views.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                   d_views.data_ptr(), n, _lib.MERGE_METRIC[metric], float(thresh), float(score_thresh),
+                                   int(bool(class_agnostic)), keep_top_k, out_dets.data_ptr(), out_count.data_ptr(),
+                                   out_src.data_ptr(), ws.data_ptr(), ws.numel(), reason, _stream())
+    if rc != _lib.OK and reason.value:
+        raise _lib.PPYoloHipError('ppy_merge_views_f32 refused the call: %s (code %d)' % (reason.value.decode(), rc))
+    check(rc, 'ppy_merge_views_f32')
 
 
 def draw_detections(h_images, images, dets, count, draw_thresh, colors, names, name_len, h_name_len, font):
