@@ -728,6 +728,40 @@ int ppy_merge_views_f32(const float *dets, const int *count, int V, int K, const
                         float *out_dets, int *out_count, int *out_src, void *ws, size_t ws_bytes, char *h_reason,
                         void *stream);
 
+/* Weighted boxes fusion of the rows of a batch of VIEWS (test-time augmentation: the whole image at several input sides,
+ * plain and mirrored) into one list per image, in the forward_padded row format (csrc/fuse_views.hip).
+ * dets, count, V, K, n as for ppy_merge_views_f32.  The view table [V][4] int32 = (image, ox, oy, mirror_w) and the view weights
+ * float32 [V] are given twice: h_views / h_view_weight on the host, where the limits are checked, and views / view_weight, their
+ * device copies, which the kernel reads.  image = -1 marks a padding view: nothing of it is read or checked.
+ *   transform:   mirror_w > 0: the row is mirrored in view coordinates first, nx0 = (float)mirror_w - x1, nx1 = (float)mirror_w
+ *                - x0 (w - x, not w - 1 - x: the decode clips boxes to [0, w]); then x += (float)ox, y += (float)oy as
+ *                ppy_merge_views_f32 translates
+ *   admission:   ppy_merge_views_f32's rule, and score > 0, and a transformed box with x1 > x0 and y1 > y0
+ *   weighted score: s = score * view_weight[v]
+ *   order:       per image, s descending, then view ascending, then row ascending
+ *   clusters:    per (image, class id), rows in that order: the row's IoU (PPY_MERGE_IOU, the row as the candidate) with the
+ *                fused box of every cluster of its class; it joins the cluster with the largest IoU STRICTLY above thresh (a tie:
+ *                the earliest created; a NaN IoU never matches): S += s, X[k] += s * b[k] (the product rounded, then the sum),
+ *                T += 1, fused[k] = X[k] / S.  Otherwise it opens a cluster: S = s, X[k] = s * b[k], T = 1, fused = the row's box
+ *                bit for bit
+ *   confidence:  wsum = the fp32 sum of view_weight over the image's non-padding views in table order; q = S / (float)T,
+ *                m = min((float)T, wsum), conf = (q * m) / wsum  (ensemble_boxes' conf_type = 'avg', one model per view)
+ *   output:      an image's clusters by conf descending, then class ascending, then creation order; the first keep_top_k:
+ *                out_dets [n][keep_top_k][6] = ((float)class id, conf, fused box), -1 behind out_count[n]; out_src int32
+ *                [n][keep_top_k][2] = (view, row) of the cluster's first member; out_members int32 [n][keep_top_k] = T; -1 padding
+ * fp32 with one rounding per operation, no fma; no floating-point atomics: two runs give the same bytes.
+ * Limits, refused and never clamped (PPY_ERR_UNSUPPORTED; h_reason, NULL or 96 chars, names the value): keep_top_k outside
+ * 1..PPY_MERGE_MAX_KEEP, K < 1, an image with more than PPY_MERGE_MAX_ROWS rows, a NaN thresh or score_thresh, a weight that is
+ * not finite and positive, mirror_w < 0.  A null pointer, n outside 1..65535, V < 1, V x K >= 2^31 or a table entry outside
+ * -1..n-1: PPY_ERR_BAD_ARG.  ws: ppy_fuse_views_workspace_bytes(n, V, K) = 64 n min(V K, PPY_MERGE_MAX_ROWS) bytes (per row
+ * the gathered row and a cluster slot, 32 bytes each), 16-byte aligned; it carries nothing from one call to the next.
+ * No host synchronisation: one launch on `stream`, one workgroup per image, capturable into a graph. */
+size_t ppy_fuse_views_workspace_bytes(int n, int V, int K);
+int ppy_fuse_views_f32(const float *dets, const int *count, int V, int K, const int *h_views, const int *views,
+                       const float *h_view_weight, const float *view_weight, int n, float thresh, float score_thresh,
+                       int keep_top_k, float *out_dets, int *out_count, int *out_src, int *out_members, void *ws,
+                       size_t ws_bytes, char *h_reason, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * conv2 -> conv3 of an identity bottleneck in ONE launch (round 5; reference model/resnet_vd.py:81-87:
  * relu(bn3(conv3(relu(bn2(conv2(t))))) + x)): conv A = 3x3 / stride 1 / pad 1, CA -> KA, BatchNorm, ReLU; conv B = 1x1, KA -> KB,

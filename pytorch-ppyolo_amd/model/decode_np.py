@@ -206,3 +206,32 @@ class Decode(object):
                 self._jpeg = JpegDecoder()
             decoder = self._jpeg
         return self.detect_tiled(decoder.decode(list(paths_or_bytes)), **kw)
+
+    def tta_detector(self, **kw):
+        """The TtaDetector (ppyolo_hip/tta.py) of these settings (scales: default this object's target size); it is kept, keyed
+        by its settings, as tiled_detector keeps its own."""
+        from ppyolo_hip.tta import TtaDetector
+        kw.setdefault('scales', (self.target_size,))
+        key = repr(sorted(kw.items()))
+        if getattr(self, '_tta_key', None) != key:
+            self._tta, self._tta_key = TtaDetector(self._yolo, self.cfg, **kw), key
+        return self._tta
+
+    def detect_tta(self, images, **kw):
+        """detect_raw with test-time augmentation: every image runs through the network at every input side of `scales`, plain
+        and mirrored, and the views' rows are fused on the device (weighted boxes fusion).  images: uint8 BGR [h,w,3] device
+        tensors (read in place) or numpy arrays; kw: TtaDetector's settings (scales, hflip, weights, thresh, score_thresh,
+        keep_top_k, batch).  Returns per image (boxes, scores, classes) in image pixels; a score is the cluster's confidence."""
+        dets, count, _, _ = self.tta_detector(**kw)(images)
+        dets, count = dets.cpu().numpy(), count.cpu().tolist()
+        empty = (np.array([]), np.array([]), np.array([]))
+        return [self._split(d[:c]) if c > 0 else empty for d, c in zip(dets, count)]
+
+    def detect_tta_files(self, paths_or_bytes, decoder=None, **kw):
+        """detect_tta from the files themselves, decoded on the device as detect_files does."""
+        if decoder is None:
+            if self._jpeg is None:
+                from ppyolo_hip.jpeg import JpegDecoder
+                self._jpeg = JpegDecoder()
+            decoder = self._jpeg
+        return self.detect_tta(decoder.decode(list(paths_or_bytes)), **kw)

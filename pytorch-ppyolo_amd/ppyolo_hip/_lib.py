@@ -230,6 +230,10 @@ _PROTOS = {
     'ppy_merge_views_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
     'ppy_merge_views_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, c_int, c_int, c_float, c_float,
                                     c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.c_char_p, c_void_p]),
+    'ppy_fuse_views_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'ppy_fuse_views_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, ctypes.POINTER(c_float), c_void_p,
+                                   c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   ctypes.c_char_p, c_void_p]),
     'ppy_nms_candidates_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p]),
     'ppy_conv3x3_conv1x1_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

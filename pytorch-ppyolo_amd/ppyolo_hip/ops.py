@@ -1002,6 +1002,53 @@ def merge_views(dets, count, h_views, d_views, n, metric, thresh, score_thresh, 
     check(rc, 'ppy_merge_views_f32')
 
 
+def fuse_views_table(views):
+    """views = a sequence of (image, ox, oy, mirror_w) -> the int32 numpy array [V, 4] fuse_views takes as its host table."""
+    tab = np.ascontiguousarray(np.asarray(views, dtype=np.int64).reshape(-1, 4))
+    if tab.size and (np.abs(tab) >= 1 << 31).any():
+        raise _lib.PPYoloHipError('view table: an entry does not fit int32')
+    return tab.astype(np.int32)
+
+
+def fuse_views_workspace(n, V, K, device):
+    """Scratch tensor for fuse_views: 64 n min(V K, 8192) bytes (empty, which the call then refuses, for n, V or K < 1)."""
+    return torch.empty(int(lib().ppy_fuse_views_workspace_bytes(int(n), int(V), int(K))), dtype=torch.uint8, device=device)
+
+
+def fuse_views(dets, count, h_views, d_views, h_weight, d_weight, n, thresh, score_thresh, keep_top_k, out_dets, out_count, out_src,
+               out_members, ws=None):
+    """Weighted boxes fusion across views (ppy_fuse_views_f32; include/ppyolo_hip.h has the contract): dets float32 [V, K, 6] and
+    count int32 [V] on the device as forward_padded writes them, h_views = fuse_views_table(...) and d_views its device copy
+    (int32 [V, 4]), h_weight float32 numpy [V] and d_weight its device copy; out_dets float32 [n, keep_top_k, 6], out_count int32
+    [n], out_src int32 [n, keep_top_k, 2], out_members int32 [n, keep_top_k].  One launch on the current stream.  A request
+    outside the limits raises PPYoloHipError naming the value."""
+    n, keep_top_k = int(n), int(keep_top_k)
+    _dev(dets, count, d_views, d_weight, out_dets, out_count, out_src, out_members)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[2] == 6
+    V, K = dets.shape[0], dets.shape[1]
+    assert count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (V,)
+    assert isinstance(h_views, np.ndarray) and h_views.dtype == np.int32 and h_views.flags.c_contiguous and h_views.shape == (V, 4)
+    assert d_views.dtype == torch.int32 and d_views.is_contiguous() and tuple(d_views.shape) == (V, 4)
+    assert isinstance(h_weight, np.ndarray) and h_weight.dtype == np.float32 and h_weight.flags.c_contiguous and h_weight.shape == (V,)
+    assert d_weight.dtype == torch.float32 and d_weight.is_contiguous() and tuple(d_weight.shape) == (V,)
+    if 1 <= keep_top_k <= _lib.MERGE_MAX_KEEP and n >= 1:      # (outside: the library refuses by name before it touches them)
+        assert out_dets.dtype == torch.float32 and out_dets.is_contiguous() and tuple(out_dets.shape) == (n, keep_top_k, 6)
+        assert out_count.dtype == torch.int32 and out_count.is_contiguous() and tuple(out_count.shape) == (n,)
+        assert out_src.dtype == torch.int32 and out_src.is_contiguous() and tuple(out_src.shape) == (n, keep_top_k, 2)
+        assert out_members.dtype == torch.int32 and out_members.is_contiguous() and tuple(out_members.shape) == (n, keep_top_k)
+    if ws is None:
+        ws = fuse_views_workspace(n, V, K, dets.device)
+    assert ws.dtype == torch.uint8 and ws.is_contiguous()
+    reason = ctypes.create_string_buffer(96)
+    rc = lib().ppy_fuse_views_f32(dets.data_ptr(), count.data_ptr(), V, K, h_views.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                  d_views.data_ptr(), h_weight.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), d_weight.data_ptr(),
+                                  n, float(thresh), float(score_thresh), keep_top_k, out_dets.data_ptr(), out_count.data_ptr(),
+                                  out_src.data_ptr(), out_members.data_ptr(), ws.data_ptr(), ws.numel(), reason, _stream())
+    if rc != _lib.OK and reason.value:
+        raise _lib.PPYoloHipError('ppy_fuse_views_f32 refused the call: %s (code %d)' % (reason.value.decode(), rc))
+    check(rc, 'ppy_fuse_views_f32')
+
+
 def draw_detections(h_images, images, dets, count, draw_thresh, colors, names, name_len, h_name_len, font):
     """Decode.draw on the device for a batch (ppyolo_hip.draw.BoxDrawer builds the tables): one launch on the current stream,
     in place.  h_images: a ctypes array of _lib.DrawImage, images: its device copy (uint8 tensor); dets [N,K,6] float32 and
