@@ -762,6 +762,68 @@ int ppy_fuse_views_f32(const float *dets, const int *count, int V, int K, const 
                        int keep_top_k, float *out_dets, int *out_count, int *out_src, int *out_members, void *ws,
                        size_t ws_bytes, char *h_reason, void *stream);
 
+/* Tracking across frames: the rows of the current frame of each of n STREAMS are associated with the stream's tracks, whose
+ * state lives in a caller-owned device buffer that the call reads and rewrites (csrc/track.hip).
+ * ByteTrack-shaped and deterministic.  dets = device float32 [n][K][6] rows (class, score, x0, y0, x1, y1), count = device
+ * int32 [n] as forward_padded writes them; count[i] < 0: stream i has no frame in this call, its state is left untouched, its
+ * out_count is 0 and its outputs are -1.  h_params is read on the host during the call.
+ *   state:       per stream 16 + 112 max_tracks bytes: a header of int32 (frame, ids issued, rows dropped for lack of a slot,
+ *                0) and max_tracks slots of 28 words: int32 state (PPY_TRACK_FREE, _NEW, _TRACKED, _LOST), id, class, float32
+ *                score, int32 hits, last (the frame of the last match), four filters for cx, cy, a = w / h, h of float32 (x, v,
+ *                Ppp, Ppv, Pvv) each, two zero words.  A FREE slot is all zero; an all-zero buffer is a fresh tracker (frame 0,
+ *                the first id is 1).  ids are int32 and are never reused.
+ *   per call and stream, in this order:
+ *   frame:       frame += 1
+ *   predict:     every slot that is not FREE: if it is not TRACKED, v_h = 0; with h = x_h before the prediction, q_pos =
+ *                (h / 20)^2, q_vel = (h / 160)^2, for the aspect filter q_pos = 1e-4f, q_vel = 1e-10f; per filter, from the old
+ *                values: x = x + v, Ppp = ((Ppp + Ppv) + (Ppv + Pvv)) + q_pos, Ppv = Ppv + Pvv, Pvv = Pvv + q_vel
+ *   box:         of a slot: w = a * h, hw = w * 0.5, hh = h * 0.5, (cx - hw, cy - hh, cx + hw, cy + hh)
+ *   admission:   row r iff r < min(count, K), all six values finite, 0 <= class < 2^24 (the id is the truncated value), x1 > x0,
+ *                y1 > y0 and score >= low_thresh; an admitted row is HIGH iff score >= high_thresh, else LOW
+ *   association: three stages of one rule: stage 1 the HIGH rows x the TRACKED and LOST slots, IoU > match_thresh[0]; stage 2
+ *                the LOW rows x the TRACKED slots stage 1 left, IoU > match_thresh[1]; stage 3 the HIGH rows stage 1 left x
+ *                the NEW slots, IoU > match_thresh[2] (states as they were before this call's update).  The rule: of all pairs
+ *                above the threshold (class_agnostic = 0: of equal class id), in the order IoU descending, then track id
+ *                ascending, then row ascending, a pair is taken iff both its ends are still free.  IoU = PPY_MERGE_IOU's
+ *                JaccardOverlap(a = the row's box, b = the slot's predicted box) with norm = 0; a NaN IoU never matches
+ *   update:      a matched slot, with z = (x0 + w * 0.5, y0 + h * 0.5, w / h, h) of the row, w = x1 - x0, h = y1 - y0:
+ *                r = (x_h / 20)^2 of the predicted x_h, 1e-2f for the aspect; per filter, from the old values: s = Ppp + r,
+ *                kp = Ppp / s, kv = Ppv / s, y = z - x, x = x + kp * y, v = v + kv * y, Ppp = Ppp - kp * Ppp, Ppv = Ppv - kp * Ppv,
+ *                Pvv = Pvv - kv * Ppv.  The slot takes the row's score and class, hits += 1, last = frame, state = TRACKED
+ *   demotion:    an unmatched TRACKED slot becomes LOST, an unmatched NEW slot FREE; then every LOST slot with frame - last >
+ *                max_lost becomes FREE; a slot that becomes FREE is zeroed
+ *   opening:     the HIGH rows still unmatched with score >= new_thresh, in row order: the lowest FREE slot, id = ++(ids
+ *                issued), state NEW (TRACKED when frame == 1), x = z, v = 0, Ppv = 0, Ppp = ((2 * h) / 20)^2 and Pvv =
+ *                ((10 * h) / 160)^2 for cx, cy and h, Ppp = 1e-4f and Pvv = 1e-10f for a; the row's score and class, hits = 1,
+ *                last = frame.  With no FREE slot the row is skipped and `dropped` counts it
+ *   output:      the TRACKED slots matched or opened in this call, by id ascending: out_dets [n][max_tracks][6] = ((float)class,
+ *                score, the slot's box after the update), out_ids, out_src (the row that matched or opened it) and out_hits
+ *                int32 [n][max_tracks]; -1 behind out_count[i]
+ * fp32 with one rounding per operation, no fma; no atomics: two runs give the same bytes, state included.
+ * Limits, refused and never clamped (PPY_ERR_UNSUPPORTED; h_reason, NULL or 96 chars, names the value): max_tracks outside
+ * 1..PPY_TRACK_MAX_TRACKS, K outside 1..PPY_TRACK_MAX_ROWS, a NaN threshold, max_lost < 0.  A null pointer, n outside 1..65535, a
+ * state that is not 16-byte aligned or shorter than ppy_track_state_bytes(n, max_tracks) (0 outside the limits):
+ * PPY_ERR_BAD_ARG.  ppy_track_workspace_bytes is 0 and ws may be NULL: between the load and the store of the state everything
+ * lives in registers and LDS (32 bytes per slot, 36 per row); the argument stays in the signature for a form that needs scratch.
+ * No host synchronisation: one launch on `stream`, one workgroup per stream, capturable into a graph (the frame counter is the
+ * kernel's).  Calls on one state must be stream-ordered. */
+#define PPY_TRACK_FREE 0
+#define PPY_TRACK_NEW 1
+#define PPY_TRACK_TRACKED 2
+#define PPY_TRACK_LOST 3
+#define PPY_TRACK_MAX_TRACKS 1024 /* a thread of the workgroup owns a slot; with 1024 rows 68 KB of the CU's 160 KB of LDS  */
+#define PPY_TRACK_MAX_ROWS 1024   /* K: a thread owns a row                                                                 */
+typedef struct ppy_track_params_t {
+    float high_thresh, low_thresh, new_thresh;
+    float match_thresh[3];
+    int max_lost, class_agnostic;
+} ppy_track_params_t;
+size_t ppy_track_state_bytes(int n, int max_tracks);
+size_t ppy_track_workspace_bytes(int n, int max_tracks, int K);
+int ppy_track_update_f32(const float *dets, const int *count, int n, int K, int max_tracks, const ppy_track_params_t *h_params,
+                         void *state, size_t state_bytes, float *out_dets, int *out_count, int *out_ids, int *out_src,
+                         int *out_hits, void *ws, size_t ws_bytes, char *h_reason, void *stream);
+
 /* ------------------------------------------------------------------------------------
  * conv2 -> conv3 of an identity bottleneck in ONE launch (round 5; reference model/resnet_vd.py:81-87:
  * relu(bn3(conv3(relu(bn2(conv2(t))))) + x)): conv A = 3x3 / stride 1 / pad 1, CA -> KA, BatchNorm, ReLU; conv B = 1x1, KA -> KB,

@@ -20,6 +20,8 @@ NORM_ACT = dict(ACT, mish=3)      # PPY_ACT_MISH: ppy_group_norm_f32 only (the c
 GN_MAX_CHUNKS = 128               # PPY_GN_MAX_CHUNKS
 MERGE_METRIC = {'iou': 0, 'ios': 1}                                              # PPY_MERGE_IOU / PPY_MERGE_IOS
 MERGE_MAX_ROWS, MERGE_RANK_MAX, MERGE_CHUNK, MERGE_MAX_KEEP = 8192, 1024, 64, 1024      # PPY_MERGE_* (include/ppyolo_hip.h)
+TRACK_FREE, TRACK_NEW, TRACK_TRACKED, TRACK_LOST = 0, 1, 2, 3                    # PPY_TRACK_FREE .. PPY_TRACK_LOST
+TRACK_MAX_TRACKS, TRACK_MAX_ROWS = 1024, 1024                                    # PPY_TRACK_MAX_TRACKS, PPY_TRACK_MAX_ROWS
 
 
 class PPYoloHipError(RuntimeError):
@@ -98,6 +100,12 @@ class DrawImage(ctypes.Structure):
 class PilImage(ctypes.Structure):
     """ppy_pil_image_t (include/ppyolo_hip.h)."""
     _fields_ = [('base', c_void_p), ('pitch', c_longlong), ('h', c_int), ('w', c_int)]
+
+
+class TrackParams(ctypes.Structure):
+    """ppy_track_params_t (include/ppyolo_hip.h)."""
+    _fields_ = [('high_thresh', c_float), ('low_thresh', c_float), ('new_thresh', c_float), ('match_thresh', c_float * 3),
+                ('max_lost', c_int), ('class_agnostic', c_int)]
 
 
 PIL_FILTERS = {0: 'nearest', 1: 'lanczos', 2: 'bilinear', 3: 'bicubic', 4: 'box', 5: 'hamming'}      # Pillow's codes (ppy_pil_resize_plan)
@@ -234,6 +242,10 @@ _PROTOS = {
     'ppy_fuse_views_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, ctypes.POINTER(c_int), c_void_p, ctypes.POINTER(c_float), c_void_p,
                                    c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                    ctypes.c_char_p, c_void_p]),
+    'ppy_track_state_bytes': (c_size_t, [c_int, c_int]),
+    'ppy_track_workspace_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'ppy_track_update_f32': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(TrackParams), c_void_p, c_size_t, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, ctypes.c_char_p, c_void_p]),
     'ppy_nms_candidates_f32': (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                        c_int, c_void_p]),
     'ppy_conv3x3_conv1x1_f32': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1049,6 +1049,39 @@ def fuse_views(dets, count, h_views, d_views, h_weight, d_weight, n, thresh, sco
     check(rc, 'ppy_fuse_views_f32')
 
 
+def track_state(n, max_tracks, device):
+    """A fresh tracker state for n streams: ppy_track_state_bytes(n, max_tracks) zero bytes (empty, which the call then refuses,
+    outside the limits)."""
+    return torch.zeros(int(lib().ppy_track_state_bytes(int(n), int(max_tracks))), dtype=torch.uint8, device=device)
+
+
+def track_update(dets, count, params, state, max_tracks, out_dets, out_count, out_ids, out_src, out_hits):
+    """One frame of every stream through the tracker (ppy_track_update_f32; include/ppyolo_hip.h has the contract): dets float32
+    [n, K, 6] and count int32 [n] on the device as forward_padded writes them, params a _lib.TrackParams, state the uint8 tensor of
+    track_state(n, max_tracks, ...), read and rewritten; out_dets float32 [n, max_tracks, 6], out_count int32 [n], out_ids, out_src
+    and out_hits int32 [n, max_tracks].  One launch on the current stream.  A request outside the limits raises PPYoloHipError
+    naming the value."""
+    max_tracks = int(max_tracks)
+    _dev(dets, count, state, out_dets, out_count, out_ids, out_src, out_hits)
+    assert dets.dtype == torch.float32 and dets.is_contiguous() and dets.dim() == 3 and dets.shape[2] == 6
+    n, K = dets.shape[0], dets.shape[1]
+    assert count.dtype == torch.int32 and count.is_contiguous() and tuple(count.shape) == (n,)
+    assert isinstance(params, _lib.TrackParams)
+    assert state.dtype == torch.uint8 and state.is_contiguous()
+    if 1 <= max_tracks <= _lib.TRACK_MAX_TRACKS and n >= 1:      # (outside: the library refuses by name before it touches them)
+        assert out_dets.dtype == torch.float32 and out_dets.is_contiguous() and tuple(out_dets.shape) == (n, max_tracks, 6)
+        assert out_count.dtype == torch.int32 and out_count.is_contiguous() and tuple(out_count.shape) == (n,)
+        for t in (out_ids, out_src, out_hits):
+            assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == (n, max_tracks)
+    reason = ctypes.create_string_buffer(96)
+    rc = lib().ppy_track_update_f32(dets.data_ptr(), count.data_ptr(), n, K, max_tracks, ctypes.byref(params), state.data_ptr(),
+                                    state.numel(), out_dets.data_ptr(), out_count.data_ptr(), out_ids.data_ptr(), out_src.data_ptr(),
+                                    out_hits.data_ptr(), None, 0, reason, _stream())
+    if rc != _lib.OK and reason.value:
+        raise _lib.PPYoloHipError('ppy_track_update_f32 refused the call: %s (code %d)' % (reason.value.decode(), rc))
+    check(rc, 'ppy_track_update_f32')
+
+
 def draw_detections(h_images, images, dets, count, draw_thresh, colors, names, name_len, h_name_len, font):
     """Decode.draw on the device for a batch (ppyolo_hip.draw.BoxDrawer builds the tables): one launch on the current stream,
     in place.  h_images: a ctypes array of _lib.DrawImage, images: its device copy (uint8 tensor); dets [N,K,6] float32 and
